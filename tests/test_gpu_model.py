@@ -64,13 +64,13 @@ def test_against_reference_fixtures(M, model, case, fused, monkeypatch):
     fx = np.load(os.path.join(GOLD, "pretrain_%s.npz" % case))
     saved = {k: v.clone() for k, v in model.state_dict().items()}
     try:
-        _fixture_case(M, model, fx, monkeypatch)
+        _fixture_case(M, model, fx, monkeypatch, case)
     finally:
         model.load_state_dict(saved)
         model.zero_grad()
 
 
-def _fixture_case(M, model, fx, monkeypatch):
+def _fixture_case(M, model, fx, monkeypatch, case):
     from gm3d_amd.engine_pretrain import train_transforms
     pts = torch.from_numpy(fx["pts"]).cuda()
     samples = train_transforms(pts, draws=(torch.from_numpy(fx["scale"]), torch.from_numpy(fx["shift"])))
@@ -128,7 +128,16 @@ def _fixture_case(M, model, fx, monkeypatch):
     (13.889 * lo["MSE_mean"] + lo["Chamfer_mean"] + ll).backward()
     named = dict(model.named_parameters())
     gsq = sum(float(p.grad.double().pow(2).sum()) for p in named.values())
-    assert abs(gsq ** 0.5 - float(fx["grad_norm"])) <= 1e-5 * float(fx["grad_norm"])
+    # every live parameter's gradient norm (pretrain_bf16.npz holds the reference's fp32 norms of all 251) at the per-tensor norm
+    # bar below; the six worst are reported BEFORE the global-norm assertion, so that a miss there names its tensor
+    from tests.parity import Ledger
+    allnorm = np.load(os.path.join(GOLD, "pretrain_bf16.npz"))
+    led = Ledger("%s fp32 per-parameter gradient norms (bar 2e-5 relative + 1e-5 of the global norm)" % case)
+    noise = 1e-5 * float(fx["grad_norm"])
+    for n, g_ref in zip(allnorm["param_names"], allnorm[case + "/gradnorm_all"]):
+        led.add(str(n), abs(float(named[str(n)].grad.double().norm()) - float(g_ref)), 2e-5 * float(g_ref) + noise)
+    assert abs(gsq ** 0.5 - float(fx["grad_norm"])) <= 1e-5 * float(fx["grad_norm"]), led.report()
+    led.assert_ok()
     for key in fx.files:
         if key.startswith("grad::"):
             g = named[key[6:]].grad
