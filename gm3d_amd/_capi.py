@@ -140,6 +140,8 @@ SIGNATURES = {
     "gm3d_colsum_partial_w": [_vp, _vp, _i, _i, _vp, _i, _vp],
     "gm3d_gemm_tn_bf16_dma_pool": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "gm3d_gemm_tn_bf16_dmaw": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "gm3d_vote_sample": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
+    "gm3d_cls_tail_vote": [_vp, _i, _i, _i, _i] + [_vp] * 14 + [_i, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp],
 }
 
 

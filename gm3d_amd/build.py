@@ -31,6 +31,7 @@ SOURCES = {
     "gemm_ws.hip": [],
     "gather.hip": [],
     "attention_masked.hip": [],
+    "vote.hip": [],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

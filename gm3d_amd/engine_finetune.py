@@ -301,3 +301,216 @@ def evaluate(data_loader, model, device, npoints=1024, bf16=True):
         correct += int((logits.argmax(-1) == target).sum())
         n += target.numel()
     return {"acc1": 100.0 * correct / max(n, 1), "loss": loss / max(n, 1), "n": n}
+
+
+# --------------------------------------------------------------------------- voting evaluation
+# P/tools/runner_finetune.py:271-335 (validate_vote) and :399-461 (test_vote): per batch one FPS to point_all, then `times` votes,
+# each a host-drawn subset of the FPS order shared by the batch, the test transform PointcloudScaleAndTranslate drawn per cloud,
+# and an eval forward; the mean of the vote logits decides.  Here the host makes exactly the reference's np.random calls, in its
+# order, before anything is launched; then ONE launch builds all V*B vote clouds, ONE forward runs them (split into chunks of
+# `max_clouds`), and ONE launch computes the head of every vote, the vote mean, the argmax and the correct count.
+
+DEFAULT_VOTE_MAX_CLOUDS = 512     # clouds per forward_tokens call: B=32 x 10 votes fits in one
+
+
+def vote_point_all(npoints, n0):
+    """point_all of the vote sampling (P/tools/runner_finetune.py:284-294): POINT_ALL[npoints], capped at the cloud size."""
+    if npoints not in POINT_ALL:
+        raise NotImplementedError("npoints %d" % npoints)
+    return min(POINT_ALL[npoints], n0)
+
+
+def draw_votes(rng, point_all, npoints, times, B):
+    """The host draws of one batch, in the reference's order: per vote np.random.choice(point_all, npoints, False)
+    (runner_finetune.py:294), then per cloud uniform(2/3, 3/2, 3) and uniform(-0.2, 0.2, 3) (test_transforms =
+    PointcloudScaleAndTranslate, datasets/data_transforms.py:31-32), cast to f32 like torch.from_numpy(...).float().
+    -> subsets (V,npoints) int64, scale (V,B,3) f32, shift (V,B,3) f32 (numpy)."""
+    subsets = np.empty((times, npoints), dtype=np.int64)
+    scale = np.empty((times, B, 3), dtype=np.float32)
+    shift = np.empty((times, B, 3), dtype=np.float32)
+    for v in range(times):
+        subsets[v] = rng.choice(point_all, npoints, False)
+        for b in range(B):
+            scale[v, b] = rng.uniform(low=2. / 3., high=3. / 2., size=[3])
+            shift[v, b] = rng.uniform(low=-0.2, high=0.2, size=[3])
+    return subsets, scale, shift
+
+
+class _VoteDraws:
+    """Device copies of one batch's draws, staged through two alternating pinned buffers (asynchronous copies, like
+    GraphedFinetuneStep._draw).  Before the first stage() they hold a draw-free warm-up value (identity transform)."""
+
+    def __init__(self, times, npoints, B, device):
+        self.times, self.npoints, self.B = times, npoints, B
+        self.subsets = torch.arange(npoints, dtype=torch.long, device=device).repeat(times, 1)
+        self.scale = torch.ones(times, B, 3, dtype=torch.float32, device=device)
+        self.shift = torch.zeros(times, B, 3, dtype=torch.float32, device=device)
+        self._pin = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in (self.subsets, self.scale, self.shift))
+                     for _ in range(2)]
+        self._ev, self._i = [None, None], 0
+
+    def stage(self, rng, point_all):
+        drawn = draw_votes(rng, point_all, self.npoints, self.times, self.B)
+        i, self._i = self._i, self._i ^ 1
+        if self._ev[i] is not None:
+            self._ev[i].synchronize()
+        for pin, dev, arr in zip(self._pin[i], (self.subsets, self.scale, self.shift), drawn):
+            pin.copy_(torch.from_numpy(arr))
+            dev.copy_(pin, non_blocking=True)
+        self._ev[i] = torch.cuda.Event()
+        self._ev[i].record(torch.cuda.current_stream())
+
+
+def vote_batch(model, points, labels, subsets, scale, shift, point_all, correct, bf16=True, max_clouds=None, votes=None):
+    """The votes of one batch on the device, no host sync: FPS (B,N0,3) -> point_all, vote_sample -> (V*B,npoints,3),
+    forward_tokens in chunks of `max_clouds` clouds, cls_tail_vote.  The model must be in eval mode (callers: validate_vote,
+    GraphedVoteEval).  correct: int64 device counter (+= correct predictions).  -> (mean logits (B,cls_dim), pred (B,))."""
+    V = subsets.size(0)
+    fps_idx = ops.furthest_point_sample(points, point_all)
+    pts = ops.vote_sample(points, fps_idx, subsets, scale, shift)
+    chunk = max_clouds or DEFAULT_VOTE_MAX_CLOUDS
+    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
+        if pts.size(0) <= chunk:
+            x = model.forward_tokens(pts)
+        else:
+            x = torch.cat([model.forward_tokens(pts[i:i + chunk]) for i in range(0, pts.size(0), chunk)], dim=0)
+    return ops.cls_tail_vote(x.contiguous(), model.cls_head_finetune, labels, V, correct, votes=votes)
+
+
+class GraphedVoteEval:
+    """The votes of one batch shape captured once as a hipGraph: FPS -> vote_sample -> forward_tokens over V*B clouds ->
+    cls_tail_vote.  Static inputs: points, labels, subsets, scale and shift (the draws are made on the host per call and copied
+    in); outputs `mean` (B,cls_dim), `pred` (B,), `votes` (V,B,cls_dim) when keep_votes, and the running int64 count `correct`.
+    A call copies, stages the draws and replays: no host sync.
+
+    The graph reads the parameters, BatchNorm running statistics and bf16 weight copies where they live, so it stays valid while
+    training continues in place between calls (a flat optimizer rewrites the weights and their bf16 shadows in place).  Should
+    the parameters be re-pointed to new storage (an optimizer that flattens them built after this object), the next call
+    captures again."""
+
+    def __init__(self, model, example_points, example_labels, npoints=1024, times=10, bf16=True, rng=np.random, max_clouds=None,
+                 keep_votes=False):
+        self.model = model.module if hasattr(model, "module") else model
+        B, N0 = example_points.shape[:2]
+        self.npoints, self.times, self.bf16, self.rng, self.max_clouds = npoints, times, bf16, rng, max_clouds
+        self.point_all = vote_point_all(npoints, N0)
+        dev = example_points.device
+        self.points = example_points.detach().float().contiguous().clone()
+        self.labels = example_labels.detach().reshape(-1).to(dev, torch.long).clone()
+        self.draws = _VoteDraws(times, npoints, B, dev)
+        self.correct = torch.zeros(1, dtype=torch.long, device=dev)
+        self.votes = torch.zeros(times, B, self.model.cls_dim, dtype=torch.float32, device=dev) if keep_votes else None
+        self._capture()
+
+    def _storage(self):
+        return tuple(t.data_ptr() for t in list(self.model.parameters()) + list(self.model.buffers()))
+
+    def _body(self, correct):
+        d = self.draws
+        return vote_batch(self.model, self.points, self.labels, d.subsets, d.scale, d.shift, self.point_all, correct,
+                          bf16=self.bf16, max_clouds=self.max_clouds, votes=self.votes)
+
+    @torch.no_grad()
+    def _capture(self):
+        was = self.model.training
+        self.model.eval()
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._body(torch.zeros(1, dtype=torch.long, device=self.points.device))    # warm-up, its own counter
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self.graph = torch.cuda.CUDAGraph()
+            with streams.capture(self.graph):
+                self.mean, self.pred = self._body(self.correct)
+            torch.cuda.synchronize()
+        finally:
+            self.model.train(was)
+        self._captured = self._storage()
+
+    def __call__(self, points, labels, rng=None):
+        """rng: the host generator of this call's draws (default: the one given at construction)."""
+        if self._storage() != self._captured:
+            self._capture()
+        self.points.copy_(points, non_blocking=True)
+        self.labels.copy_(labels.reshape(-1), non_blocking=True)
+        self.draws.stage(self.rng if rng is None else rng, self.point_all)
+        self.graph.replay()
+        return self.mean, self.pred
+
+
+@torch.no_grad()
+def validate_vote(model, data_loader, device, npoints=1024, times=10, bf16=True, rng=np.random, graphed=True, max_clouds=None,
+                  outputs=False):
+    """Voting accuracy over a loader of (.., .., (points, label)) batches (P/tools/runner_finetune.py:271-335), with the same
+    np.random calls in the same order as the reference: seeded alike, both use the same subsets and transforms.
+    graphed: True -> a GraphedVoteEval is captured on the first batch and replayed for every batch of that shape (a ragged
+    last batch runs eagerly through the same kernels); a GraphedVoteEval instance is reused (its capture outlives the call; the
+    draws still come from `rng`);
+    False -> eager.  max_clouds: clouds per forward (default DEFAULT_VOTE_MAX_CLOUDS = 512; the V*B forward is split above).
+    One host sync per call, at the end.  Predictions and labels are gathered across ranks like the reference.
+    -> {"acc_vote", "n"}; outputs=True adds the local "pred" (n,), "mean" (n,cls_dim) and "votes" (V,n,cls_dim)."""
+    raw = model.module if hasattr(model, "module") else model
+    was = raw.training
+    raw.eval()
+    try:
+        g = graphed if isinstance(graphed, GraphedVoteEval) else None
+        if g is not None and outputs and g.votes is None:
+            raise ValueError("outputs=True needs a GraphedVoteEval built with keep_votes=True")
+        counter = None
+        eager_draws = {}
+        preds, labels, means, votes = [], [], [], []
+        for batch in data_loader:
+            data = batch[-1]
+            points = data[0].to(device, non_blocking=True).float().contiguous()
+            label = data[1].to(device, non_blocking=True).long().reshape(-1)
+            if g is None and graphed is True:
+                g = GraphedVoteEval(raw, points, label, npoints=npoints, times=times, bf16=bf16, rng=rng, max_clouds=max_clouds,
+                                    keep_votes=outputs)
+            if counter is None:
+                counter = g.correct if g is not None else torch.zeros(1, dtype=torch.long, device=device)
+                counter.zero_()
+            if g is not None and points.shape == g.points.shape:
+                mean, pred = g(points, label, rng=rng)
+                mean, pred = mean.clone(), pred.clone()
+                vt = g.votes.clone() if outputs else None
+            else:
+                B = points.size(0)
+                point_all = vote_point_all(npoints, points.size(1))
+                d = eager_draws.get(B)
+                if d is None:
+                    d = eager_draws[B] = _VoteDraws(times, npoints, B, points.device)
+                d.stage(rng, point_all)
+                vt = torch.empty(times, B, raw.cls_dim, dtype=torch.float32, device=points.device) if outputs else None
+                mean, pred = vote_batch(raw, points, label, d.subsets, d.scale, d.shift, point_all, counter, bf16=bf16,
+                                        max_clouds=max_clouds, votes=vt)
+            preds.append(pred)
+            labels.append(label)
+            if outputs:
+                means.append(mean)
+                votes.append(vt)
+    finally:
+        raw.train(was)
+    if not preds:
+        return {"acc_vote": 0.0, "n": 0}
+    pred, label = torch.cat(preds), torch.cat(labels)
+    from .validate import gather_tensor
+    import torch.distributed as dist
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        gp, gl = gather_tensor(pred), gather_tensor(label)
+        correct, n = int((gp == gl).sum()), gl.numel()
+    else:
+        correct, n = int(counter), label.numel()
+    # the reference's arithmetic: (pred == label).sum() / float(n) * 100. in float32
+    acc = float(torch.tensor(correct) / float(n) * 100.)
+    out = {"acc_vote": acc, "n": n}
+    if outputs:
+        out.update(pred=pred, mean=torch.cat(means), votes=torch.cat(votes, dim=1))
+    return out
+
+
+def test_vote(model, data_loader, device, npoints=1024, times=10, bf16=True, rng=np.random, graphed=True, max_clouds=None):
+    """P/tools/runner_finetune.py:399-461: the same voting pass as validate_vote; returns the accuracy."""
+    return validate_vote(model, data_loader, device, npoints=npoints, times=times, bf16=bf16, rng=rng, graphed=graphed,
+                         max_clouds=max_clouds)["acc_vote"]

@@ -141,6 +141,74 @@ def gather_operation(features, idx):
     return _GatherOperation.apply(features, idx)
 
 
+# ------------------------------------------------------------------ voting evaluation (tools/runner_finetune.py:271-335)
+def vote_sample(points, fps_idx, subsets, scale, shift, out=None):
+    """All vote clouds of a batch in one launch: points (B,N0,3) f32, fps_idx (B,point_all) int32, subsets (V,npoints) int64,
+    scale / shift (V,B,3) f32 -> (V*B,npoints,3) f32, row v*B+b = points[b][fps_idx[b][subsets[v]]] * scale[v,b] + shift[v,b]
+    (bit-equal to index_select + gather_operation + the reference's `pc*xyz1 + xyz2`)."""
+    _require(points, torch.float32, "points")
+    _require(fps_idx, torch.int32, "fps_idx")
+    _require(subsets, torch.int64, "subsets")
+    _require(scale, torch.float32, "scale")
+    _require(shift, torch.float32, "shift")
+    if points.dim() != 3 or points.size(2) != 3 or fps_idx.dim() != 2 or fps_idx.size(0) != points.size(0) or subsets.dim() != 2:
+        raise RuntimeError("points must be (B,N0,3), fps_idx (B,point_all), subsets (V,npoints)")
+    B, N0, _ = points.shape
+    P = fps_idx.size(1)
+    V, npoints = subsets.shape
+    if tuple(scale.shape) != (V, B, 3) or tuple(shift.shape) != (V, B, 3):
+        raise RuntimeError("scale and shift must be (V,B,3) = (%d,%d,3)" % (V, B))
+    if out is None:
+        out = torch.empty(V * B, npoints, 3, dtype=torch.float32, device=points.device)
+    _require(out, torch.float32, "out")
+    if tuple(out.shape) != (V * B, npoints, 3):
+        raise RuntimeError("out must be (V*B,npoints,3)")
+    _launch("gm3d_vote_sample", {"B": B, "N0": N0, "point_all": P, "npoints": npoints, "V": V}, lib.gm3d_vote_sample, _ptr(points),
+            _ptr(fps_idx), _ptr(subsets), _ptr(scale), _ptr(shift), B, N0, P, npoints, V, _ptr(out), _stream())
+    return out
+
+
+def cls_tail_vote(x, head, labels, V, correct, votes=None):
+    """Eval-mode classification head of PointTransformer (cls_head_finetune: Linear, BN, ReLU, Dropout, Linear, BN, ReLU, Dropout,
+    Linear) on the stack output x (V*B,T,384) f32/bf16 of all V votes, then the vote mean and its argmax, in one launch.
+    head: the nn.Sequential (its parameters and running statistics are read by the kernel on every call).  labels (B,) int64;
+    correct: int64 device counter, incremented by the number of correct predictions.  votes: optional (V,B,cls_dim) f32 output.
+    -> (mean logits (B,cls_dim) f32, pred (B,) int64)."""
+    _require(x, None, "x")
+    if x.dtype not in _DT:
+        raise RuntimeError("x must be float32 or bfloat16")
+    _require(labels, torch.int64, "labels")
+    _require(correct, torch.int64, "correct")
+    l1, bn1, l2, bn2, l3 = head[0], head[1], head[4], head[5], head[8]
+    if bn1.eps != bn2.eps:
+        raise RuntimeError("both BatchNorm layers of the head must share eps")
+    ps = [l1.weight, l1.bias, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var,
+          l2.weight, l2.bias, bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var, l3.weight, l3.bias]
+    for i, p in enumerate(ps):
+        _require(p, torch.float32, "head tensor %d" % i)
+    cls_dim = l3.weight.size(0)
+    want = [(256, 768)] + [(256,)] * 5 + [(256, 256)] + [(256,)] * 5 + [(cls_dim, 256), (cls_dim,)]
+    if [tuple(p.shape) for p in ps] != want:
+        raise RuntimeError("head must be Linear(768,256), BN(256), ReLU, Dropout, Linear(256,256), BN(256), ReLU, Dropout, "
+                           "Linear(256,cls_dim)")
+    if x.dim() != 3 or x.size(0) % V:
+        raise RuntimeError("x must be (V*B,T,C)")
+    R, T, C = x.shape
+    B = R // V
+    if labels.numel() != B:
+        raise RuntimeError("labels must hold B = %d entries" % B)
+    mean = torch.empty(B, cls_dim, dtype=torch.float32, device=x.device)
+    pred = torch.empty(B, dtype=torch.int64, device=x.device)
+    if votes is not None:
+        _require(votes, torch.float32, "votes")
+        if tuple(votes.shape) != (V, B, cls_dim):
+            raise RuntimeError("votes must be (V,B,cls_dim)")
+    _launch("gm3d_cls_tail_vote", {"V": V, "B": B, "T": T, "cls_dim": cls_dim}, lib.gm3d_cls_tail_vote, _ptr(x), int(V), B, T, C,
+            *[_ptr(p) for p in ps], cls_dim, float(bn1.eps), _ptr(labels), _ptr(mean), _ptr(pred), _ptr(correct), _ptr(votes),
+            _DT[x.dtype], _stream())
+    return mean, pred
+
+
 # ------------------------------------------------------------------ KNN / grouping
 def knn(ref, query, k, return_dist=True):
     ref = ref.detach().contiguous()

@@ -108,15 +108,19 @@ class PointTransformer(nn.Module):
             return heads.PosEmbedFn.apply(center, l0.weight, l0.bias, l1.weight, l1.bias, heads._adt())
         return l1(act(linear3(center, l0.weight, l0.bias)))
 
-    def forward_features(self, pts):
-        """-> (B, 2*trans_dim): [cls token ; max over the patch tokens] after the 12 blocks and norm_p (P/:565-573)."""
+    def forward_tokens(self, pts):
+        """-> (B, 1 + num_group, trans_dim): the token stack after the 12 blocks and norm_p (P/:565-573)."""
         neighborhood, center, _ = self.group_divider(pts)
         tokens = self.encoder(neighborhood)                                   # B G C
         B = tokens.size(0)
         pos = self.embed_pos(center)
         x = torch.cat((self.cls_token.expand(B, -1, -1).to(tokens.dtype), tokens), dim=1)
         pos = torch.cat((self.cls_pos.expand(B, -1, -1).to(pos.dtype), pos), dim=1)
-        x = self.blocks(x, pos, norm=self.norm_p)                             # fused stack + norm_p
+        return self.blocks(x, pos, norm=self.norm_p)                          # fused stack + norm_p
+
+    def forward_features(self, pts):
+        """-> (B, 2*trans_dim): [cls token ; max over the patch tokens] of forward_tokens (P/:575)."""
+        x = self.forward_tokens(pts)
         return torch.cat([x[:, 0], x[:, 1:].max(1)[0]], dim=-1)
 
     def forward(self, pts):

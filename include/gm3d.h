@@ -612,6 +612,32 @@ int gm3d_attention_masked_fwd(const void *qkv, const unsigned *mask, void *out, 
 int gm3d_attention_masked_bwd(const void *qkv, const unsigned *mask, const void *out, const void *dout, const float *lse, void *dqkv,
                               int B, int T, int H, int HD, float scale, int dtype, gm3d_stream_t stream);
 
+/* ---- Voting evaluation of the fine-tuned classifier (gm3d_amd/csrc/vote.hip) --------------------------------------------
+ * Replaces the per-vote loop of validate_vote / test_vote (Point-MAE_SA3D/tools/runner_finetune.py:293-309 and :421-437):
+ * V times fps_idx_raw[:, np.random.choice(point_all, npoints, False)], gather_operation, test_transforms
+ * (PointcloudScaleAndTranslate, datasets/data_transforms.py:27-35) and base_model(points), then the vote mean and argmax.
+ *
+ * gm3d_vote_sample: points (B,N0,3) f32, fps_idx (B,point_all) int32, subsets (V,npoints) int64, scale / shift (V,B,3) f32 ->
+ * out (V*B,npoints,3) f32, vote-major (row v*B+b) = points[b][fps_idx[b][subsets[v][j]]] * scale[v][b] + shift[v][b], product and
+ * sum rounded separately (bit-equal to the torch op chain).  An index out of range yields a NaN point.
+ * Limits: npoints <= point_all <= N0.
+ *
+ * gm3d_cls_tail_vote: the eval-mode cls_head_finetune (P/models/Point_MAE.py:489-499, :575-577) on the stack output after norm_p,
+ * x (V*B,T,C) in `dtype` (16-byte aligned), for all V votes of every cloud, plus the vote mean and its argmax:
+ * feature = [x[:,0] ; max over tokens 1..T-1], Linear W1 (256,2C) b1, BatchNorm (g1, be1, running rm1 / rv1, eps), ReLU,
+ * Linear W2 (256,256) b2, BatchNorm (g2, be2, rm2, rv2, eps), ReLU, Linear W3 (cls_dim,256) b3 (Dropout = identity); all f32,
+ * the running statistics are read on every call.  mean (B,cls_dim) f32 = sum of the votes in order v = 0..V-1, then / V;
+ * pred (B) int64 = argmax (ties -> lowest index); *correct += number of b with pred[b] == labels[b] (int64, no float atomics);
+ * votes (V,B,cls_dim) f32 per-vote logits, or NULL.
+ * Limits: C == 384, T >= 2, 1 <= cls_dim <= 256, 1 <= V <= 16. */
+int gm3d_vote_sample(const float *points, const int32_t *fps_idx, const long long *subsets, const float *scale, const float *shift,
+                     int B, int N0, int point_all, int npoints, int V, float *out, gm3d_stream_t stream);
+int gm3d_cls_tail_vote(const void *x, int V, int B, int T, int C, const float *W1, const float *b1, const float *g1, const float *be1,
+                       const float *rm1, const float *rv1, const float *W2, const float *b2, const float *g2, const float *be2,
+                       const float *rm2, const float *rv2, const float *W3, const float *b3, int cls_dim, float eps,
+                       const long long *labels, float *mean, long long *pred, long long *correct, float *votes, int dtype,
+                       gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
