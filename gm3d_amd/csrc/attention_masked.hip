@@ -531,8 +531,13 @@ extern "C" int gm3d_radius_mask_bits_m(const float* center, const unsigned char*
     if (B == 0) return GM3D_OK;
     const int W = (G + 31) / 32;
     if (G > 8192 || B > 65535) return GM3D_EUNSUPPORTED;
-    hipLaunchKernelGGL(radius_mask_bits_kernel, dim3((unsigned)((G * W + 255) / 256), (unsigned)B), dim3(256), (size_t)4 * G * sizeof(float),
-                       (hipStream_t)stream, center, vis, radius, B, G, W, bits, inv);
+    const size_t lds = (size_t)4 * G * sizeof(float);       // G > 4096: above the 64 KiB default, up to 128 KiB at G = 8192
+    if (lds > 64 * 1024) {
+        static LdsAttr attr;
+        if (!attr.ensure((const void*)radius_mask_bits_kernel, lds)) return GM3D_ELAUNCH;
+    }
+    hipLaunchKernelGGL(radius_mask_bits_kernel, dim3((unsigned)((G * W + 255) / 256), (unsigned)B), dim3(256), lds, (hipStream_t)stream,
+                       center, vis, radius, B, G, W, bits, inv);
     GM3D_CHECK_LAUNCH();
     return GM3D_OK;
 }

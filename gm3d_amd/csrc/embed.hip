@@ -925,6 +925,11 @@ static inline int slices_for(int C) { const int tpr = C / 8; int sl = 256 / tpr;
 static inline int group_grid(int G) { return G < 1024 ? G : 1024; }
 static inline int row_grid(int R, int C) { const int sl = slices_for(C); int g = (R + sl - 1) / sl; return g < 1 ? 1 : (g > 1024 ? 1024 : g); }
 static inline int moments_grid(int R) { int g = (R + 255) / 256; return g < 1 ? 1 : (g > 256 ? 256 : g); }
+// fp64 row-slice reductions: sl slices of C / 8 threads, an LDS tile of sl * q * C doubles (q = 5 for pn_layer1_bwd_stats, 4 for
+// lin3_gelu_bwd) kept within the 64 KiB a launch gets without hipFuncSetAttribute
+static inline int pn1_slices(int C1) { return C1 > 200 ? 4 : 8; }     // C1 = 256: 4 * 5 * 256 * 8 B = 40 KiB (8 slices: 80 KiB)
+static inline int lin3_slices(int C) { return C > 256 ? 4 : 8; }      // C = 256 and C = 512: exactly 64 KiB
+static inline int slice_grid(int R, int sl) { int g = (R + sl - 1) / sl; return g > 1024 ? 1024 : (g < 1 ? 1 : g); }
 
 }  // namespace gm3d
 
@@ -935,7 +940,8 @@ extern "C" int gm3d_embed_partial_rows(int kind, int n, int C) {
     using namespace gm3d;
     if (kind == 0) return moments_grid(n);        // moments3: n = rows
     if (kind == 1) return group_grid(n);          // (G,K,C) kernels: n = groups
-    if (kind == 3) { const int sl = C > 256 ? 4 : 8; int g = (n + sl - 1) / sl; return g > 1024 ? 1024 : (g < 1 ? 1 : g); }   // gm3d_lin3_gelu_bwd (8 row slices per workgroup, 4 for C > 256)
+    if (kind == 3) return slice_grid(n, lin3_slices(C));      // gm3d_lin3_gelu_bwd: n = rows
+    if (kind == 4) return slice_grid(n, pn1_slices(C));       // gm3d_pn_layer1_bwd_stats: n = rows
     return row_grid(n, C);                        // (R,C) kernels: n = rows
 }
 
@@ -1201,9 +1207,9 @@ extern "C" int gm3d_pn_layer1_bwd_stats(const void* da1, const void* a1, const f
     if (!da1 || !a1 || !x || !w1 || !b1 || !mean || !rstd || !xmean || !partial || R < 1) return GM3D_EINVAL;
     if (!chan_ok(C1) || C1 > 256) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
-    const int tpr = C1 / 8, sl = 8;                       // 8 slices: fp64 LDS tile stays under 64 KB
+    const int tpr = C1 / 8, sl = pn1_slices(C1);          // fp64 LDS tile at most 64 KiB (C1 <= 200: 8 slices, else 4)
     const size_t lds = (size_t)sl * 5 * C1 * sizeof(double);
-    int grid = (R + sl - 1) / sl; grid = grid > 1024 ? 1024 : grid;
+    const int grid = slice_grid(R, sl);
     hipStream_t st = (hipStream_t)stream;
     GM3D_DISPATCH(dtype,
                   hipLaunchKernelGGL(pn_layer1_bwd_stats_kernel<bf16_t>, dim3(grid), dim3(sl * tpr), lds, st,
@@ -1276,9 +1282,9 @@ extern "C" int gm3d_lin3_gelu_bwd(const void* dout, const float* x, const float*
     if (!dout || !x || !w || !b || !partial || R < 1) return GM3D_EINVAL;
     if (!chan_ok(C) || C > 512) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
-    const int tpr = C / 8, sl = C > 256 ? 4 : 8;       // C = 384: 192 threads, 48 KiB of fp64 partials
+    const int tpr = C / 8, sl = lin3_slices(C);        // C = 384: 192 threads, 48 KiB of fp64 partials
     const size_t lds = (size_t)sl * 4 * C * sizeof(double);
-    int grid = (R + sl - 1) / sl; grid = grid > 1024 ? 1024 : grid;
+    const int grid = slice_grid(R, sl);
     hipStream_t st = (hipStream_t)stream;
     GM3D_DISPATCH(dtype,
                   hipLaunchKernelGGL(lin3_gelu_bwd_kernel<bf16_t>, dim3(grid), dim3(sl * tpr), lds, st, (const bf16_t*)dout, x, w, b, R, C, partial),

@@ -280,7 +280,7 @@ class EmbedFn(torch.autograd.Function):
         dW2 = wgrad(df, a1).reshape(w2.shape)
         # layer 1: BN1 + conv(K=3), reductions only
         W1 = _c32(w1.reshape(C1, 3))
-        nrows = lib.gm3d_embed_partial_rows(3, R, C1)
+        nrows = lib.gm3d_embed_partial_rows(4, R, C1)
         part = torch.empty(nrows, 5 * C1, dtype=f64, device=dev)
         b1f, g1f = _c32(b1), _c32(g1)
         _launch("gm3d_pn_layer1_bwd_stats", {"R": R, "C": C1, "dtype": str(adt)}, lib.gm3d_pn_layer1_bwd_stats, _ptr(da1),

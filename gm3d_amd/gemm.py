@@ -18,7 +18,7 @@ def supported(x, w):
     """x (M,K) bf16 with unit inner stride, w (N,K) bf16 contiguous rows; N % 128 == 0, K % 64 == 0."""
     return (ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.dim() == 2 and w.dim() == 2
             and x.shape[1] == w.shape[1] and w.shape[0] % 128 == 0 and w.shape[1] % 64 == 0 and x.stride(1) == 1
-            and w.stride(1) == 1 and x.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1]
+            and w.stride(1) == 1 and x.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1] and w.stride(0) >= w.shape[1]
             and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
 
 
@@ -29,7 +29,7 @@ def ragged_supported(x, w):
     """the plain product on csrc/gemm.hip's ragged form: N, K any multiples of 8 (W rows past N clamped, the last K-stage zero-filled)."""
     return (ENABLED and RAGGED and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.dim() == 2 and w.dim() == 2
             and x.shape[1] == w.shape[1] and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0 and w.shape[1] >= 8 and x.stride(1) == 1
-            and w.stride(1) == 1 and x.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1]
+            and w.stride(1) == 1 and x.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1] and w.stride(0) >= w.shape[1]
             and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
 
 
@@ -424,6 +424,7 @@ def wgrad_supported(dy, x):
     return (ENABLED and OWN_WGRAD and dy.is_cuda and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and dy.dim() == 3
             and x.dim() == 3 and dy.shape[:2] == x.shape[:2] and dy.shape[2] % edge == 0 and x.shape[2] % edge == 0
             and dy.shape[1] % 32 == 0 and dy.stride(2) == 1 and x.stride(2) == 1 and dy.stride(1) % 8 == 0 and x.stride(1) % 8 == 0
+            and dy.stride(1) >= dy.shape[2] and x.stride(1) >= x.shape[2]
             and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and (dy.shape[0] == 1 or (dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0)))
 
 

@@ -250,7 +250,7 @@ class GroupMaxFn(torch.autograd.Function):
 
 
 def group_max_supported(x):
-    return x.is_cuda and x.dim() == 3 and x.dtype in _DT and x.shape[2] % 8 == 0 and 1 <= x.shape[1] <= 255 and x.shape[2] <= 1024
+    return x.is_cuda and x.dim() == 3 and x.dtype in _DT and x.shape[2] % 8 == 0 and 1 <= x.shape[1] <= 255 and 8 <= x.shape[2] <= 1024
 
 
 class Interp3Fn(torch.autograd.Function):

@@ -215,7 +215,8 @@ int gm3d_gelu_partial_rows(int R);
  * Together with the GEMMs they restate Encoder.forward (Point-MAE_SA3D/models_mae_learn_loss.py:868-899) and its
  * backward.  Activations are (G groups, K points, C channels) row-major in `dtype`; C % 8 == 0, C <= 1024, K <= 255.
  * Kernels that reduce over rows write per-workgroup partial rows; gm3d_embed_partial_rows(kind, n, C) gives the
- * number of rows (kind 0: gm3d_moments3, n = rows; kind 1: (G,K,C) kernels, n = G; kind 2: (R,C) kernels, n = R; kind 3: gm3d_pn_layer1_bwd_stats, n = R),
+ * number of rows (kind 0: gm3d_moments3, n = rows; kind 1: (G,K,C) kernels, n = G; kind 2: (R,C) kernels, n = R; kind 3: gm3d_lin3_gelu_bwd, n = R;
+ * kind 4: gm3d_pn_layer1_bwd_stats, n = R),
  * and gm3d_colsum_finish adds them up. */
 int gm3d_embed_partial_rows(int kind, int n, int C);
 
@@ -290,7 +291,7 @@ int gm3d_group_scatter_add(void *df, const void *dfg, const uint8_t *arg, int G,
 
 /* Backward reductions of Conv1d(3,C1)+BatchNorm+ReLU: with g1 = da1*[a1>0], hhat = (x.w1+b1-mean)*rstd,
  * xc = x - xmean (xmean (3) f32): partial[row][q][c] in fp64 (the weight gradient is a small difference of these
- * sums), q = 0: sum g1, 1: sum g1*hhat, 2..4: sum g1*xc_j; rows = gm3d_embed_partial_rows(3, R, C1); C1 <= 256. */
+ * sums), q = 0: sum g1, 1: sum g1*hhat, 2..4: sum g1*xc_j; rows = gm3d_embed_partial_rows(4, R, C1); C1 <= 256. */
 int gm3d_pn_layer1_bwd_stats(const void *da1, const void *a1, const float *x, const float *w1, const float *b1,
                              const float *mean, const float *rstd, const float *xmean, int R, int C1,
                              double *partial, int dtype, gm3d_stream_t stream);
@@ -556,8 +557,9 @@ int gm3d_gemm_nt_bf16_multi(int count, const void *const *dY, const void *const 
  * word j>>5 of row i set = query i must not attend to key j (NULL: no mask); the mask must be symmetric.  out (B,T,H*HD), lse
  * (B,H,T) f32 (0 for a query with no allowed key, whose output and gradients are zero).  dtype GM3D_BF16: flash-style MFMA
  * kernels; GM3D_F32: exact fp32 kernels (parity mode).  bf16 keeps the head in LDS: the forward needs (2*32*ceil(T/32) + 128) *
- * (2 HD + 16) bytes, the backward 4*32*ceil(T/32) * (2 HD + 16) + 8*32*ceil(T/32), at most 160 KiB -- i.e. T <= 512 for HD <= 32
- * and, for HD = 64, T <= 480 forward / T <= 256 backward (GM3D_EUNSUPPORTED beyond).  With mask = NULL and HD = 64 these are also
+ * (2 HD + 16) bytes, the backward 4*32*ceil(T/32) * (2 HD + 16) + 8*32*ceil(T/32), at most 160 KiB -- i.e. T <= 512 for HD = 16,
+ * T <= 512 forward / T <= 480 backward for HD = 32 and T <= 480 forward / T <= 256 backward for HD = 64 (GM3D_EUNSUPPORTED
+ * beyond).  With mask = NULL and HD = 64 these are also
  * the attention of the Point-MAE models for more than 128 tokens (cfgs/config_3.yaml: 256 groups). */
 /* Deterministic backward of a row gather with repeated indices (the hierarchical model's member / 3-NN token gathers: PyTorch's
  * gather backward scatter-adds with colliding float atomics).  gm3d_gather_inverse: idx (B,J) int64 with values in [0,S) -> the
@@ -567,7 +569,8 @@ int gm3d_gather_inverse(const long long *idx, int B, int J, int S, int *off, int
 int gm3d_gather_rows_bwd(const void *dy, const int *off, const int *list, void *dx, int B, int J, int S, int C, int dtype,
                          gm3d_stream_t stream);
 /* The bitset mask of one level of the hierarchical encoder: bits (B,G,ceil(G/32)), bit j of row i set iff token i or token j is
- * not visible (vis (B,G) bytes, NULL = all visible) or their centres (B,G,3) are >= radius apart (radius <= 0: no radius test). */
+ * not visible (vis (B,G) bytes, NULL = all visible) or their centres (B,G,3) are >= radius apart (radius <= 0: no radius test).
+ * G <= 8192, B <= 65535 (GM3D_EUNSUPPORTED beyond). */
 int gm3d_radius_mask_bits(const float *center, const unsigned char *vis, float radius, int B, int G, unsigned *bits,
                           gm3d_stream_t stream);
 /* ... with the flags' sense selectable: flags_are_masked != 0 -> a non-zero byte means NOT visible (the multi-scale masks as they are) */
