@@ -3,6 +3,7 @@
 `python -m gm3d_amd.build` or `gm3d_amd.build.build()`.  hipcc cross-compiles without a
 GPU; the resulting .so is git-ignored but travels with the working tree.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -46,7 +47,7 @@ def _stale(target, deps):
 def build(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OUT_DIR, exist_ok=True)
-    hdrs = [os.path.join(CSRC, "common.hpp"), os.path.join(HERE, "..", "include", "gm3d.h")]
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "gm3d.h")]
     objs = []
     for src, extra in SOURCES.items():
         s = os.path.join(CSRC, src)

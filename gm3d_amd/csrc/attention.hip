@@ -19,36 +19,18 @@
 // Backward recomputes P from the saved log-sum-exp; NT waves each own one 32-key tile (dK/dV) and NT more waves each own
 // one 32-query tile (dQ), side by side in the same workgroup: no atomics, no cross-workgroup sums.
 // Kernels are templated on MT, the number of 32-row tiles the LDS buffers hold (2: T <= 64, 4: T <= 128).
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace gm3d {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int HD = 64;        // head dim
 constexpr int VLD = 72;       // bf16 LDS row pitch (144 B: 16-B aligned rows)
 
-// C/D layout of a 32x32 MFMA: column = lane & 31, row = crow(reg, lane >> 5).
-__device__ __forceinline__ int crow(int g, int hh) { return (g & 3) + 8 * (g >> 2) + 4 * hh; }
 // k index (0..31) carried by element j of lane half hh at k-step s when accumulator
 // registers 8s..8s+7 are reused as a bf16 operand: equals crow(8s + j, hh).
 __device__ __forceinline__ int permk(int s, int j, int hh) { return 16 * s + 8 * (j >> 2) + 4 * hh + (j & 3); }
 
 __device__ __forceinline__ bf16x8 ld8(const bf16_t* p) { return *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ bf16x8 zero8() {
-    bf16x8 z;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z[j] = (bf16_t)0.0f;
-    return z;
-}
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) z[g] = 0.f;
-    return z;
-}
 // 8 elements M[row][k], k = permk order of k-step s inside the 32-wide tile starting at k0
 __device__ __forceinline__ bf16x8 ld8_perm(const bf16_t* row, int k0, int s, int hh) {
     const bf16x4 a = *reinterpret_cast<const bf16x4*>(row + k0 + 16 * s + 4 * hh);
@@ -65,14 +47,7 @@ __device__ __forceinline__ bf16x8 ld8_col_perm(const bf16_t* M, int ld, int k0, 
     for (int j = 0; j < 8; ++j) v[j] = M[(size_t)(k0 + permk(s, j, hh)) * ld + col];
     return v;
 }
-__device__ __forceinline__ bf16x8 cvt8(const f32x16& x, int s, float mul) {
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (bf16_t)(x[8 * s + j] * mul);
-    return v;
-}
 
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 #define MFMA_F32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0)
 
 // Cooperative copy of one head's (T,64) slice of qkv into a zero-padded `rows`-row LDS tile.
@@ -93,17 +68,13 @@ __device__ __forceinline__ void stage_f32(float* dst /*[rows*64]*/, const float*
 }
 
 // ===================================================================== LDS images (bf16 kernels)
-// A head's (T,64) bf16 slice lives in LDS as a swizzled [rows][64] image with 128-byte rows and NO padding: the 16-byte chunk
-// ch (0..7) of row `row` sits at byte 128*row + 16*(ch ^ f(row)), f = the bit-reversed (row >> 1) & 7.  One image serves both
-// kinds of MFMA operand read conflict-free (bank rule of ds_read_b128 / ds_read_b64_tr_b16: 64 banks, MI355X_MICROARCH.md LDS):
-//   row read   (ds_read_b128):        a 16-lane group reads one chunk of 16 different rows -> f spreads them over all 16 slots;
-//   transposed (ds_read_b64_tr_b16):  a 32-lane half reads 4 consecutive rows x 32 columns -> (row & 1, f bit 2) picks a
-//                                     different 64-byte quarter of the bank row for each of the four rows.
+// A head's (T,64) bf16 slice lives in LDS as a swizzled [rows][64] image: 128-byte rows, chunk order swz (mfma.hpp).  img_off (=
+// swz_off) and the two LDS-DMA source swizzles of attn_qkv_fwd_bf16_kernel (= swz) keep their own form: through the shared
+// functions the compiler schedules and allocates these kernels differently.
 __device__ __forceinline__ int img_off(int row, int ch) {
-    const int f = (((row >> 1) & 1) << 2) | (((row >> 2) & 1) << 1) | ((row >> 3) & 1);
+    const int f = swz(row);
     return row * 128 + ((ch ^ f) << 4);
 }
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 // operand fragment read along a row: 8 consecutive d (chunk ch) of row `row`
 __device__ __forceinline__ bf16x8 img_row(const unsigned char* img, int row, int ch) {
     return *reinterpret_cast<const bf16x8*>(img + img_off(row, ch));
@@ -171,7 +142,7 @@ __device__ __forceinline__ void attn_core_bf16(const unsigned char* Qi, const un
     for (int s = 0; s < 4; ++s) {
         const bf16x8 bq = img_row(Qi, qrow, 2 * s + hh);
 #pragma unroll
-        for (int t = 0; t < NT; ++t) st[t] = MFMA_BF16(img_row(Ki, 32 * t + r, 2 * s + hh), bq, st[t]);
+        for (int t = 0; t < NT; ++t) st[t] = mfma_bf16(img_row(Ki, 32 * t + r, 2 * s + hh), bq, st[t]);
     }
     float m = -INFINITY;
 #pragma unroll
@@ -203,8 +174,8 @@ __device__ __forceinline__ void attn_core_bf16(const unsigned char* Qi, const un
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const bf16x8 p = cvt8(st[t], s, inv);
-            o0 = MFMA_BF16(img_tr8(Vi, 32 * t, s, hh, cb, lane), p, o0);
-            o1 = MFMA_BF16(img_tr8(Vi, 32 * t, s, hh, 32 + cb, lane), p, o1);
+            o0 = mfma_bf16(img_tr8(Vi, 32 * t, s, hh, cb, lane), p, o0);
+            o1 = mfma_bf16(img_tr8(Vi, 32 * t, s, hh, 32 + cb, lane), p, o1);
         }
     store_tile_t(Oi, 32 * w, o0, o1, lane, outp, os, T);
     if (lsep && hh == 0 && qrow < T) lsep[qrow] = m + logf(sum);
@@ -260,14 +231,6 @@ __global__ __launch_bounds__(64 * NT) void attn_fwd_bf16_kernel(const bf16_t* __
 // heads on one XCD (its token tile is fetched from HBM once, then hit in that XCD's L2).
 constexpr int QA_C = 384, QA_KT = QA_C / 64, QA_STAGE = (64 + 192) * 128;
 
-__device__ __forceinline__ void qa_glds16(const void* gsrc, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(dst)
-                 : "memory");
-}
-
 template <int LOOK, bool WRITE_QKV>
 __global__ __launch_bounds__(256) void attn_qkv_fwd_bf16_kernel(const bf16_t* __restrict__ hin, const bf16_t* __restrict__ wqkv,
                                                                 bf16_t* __restrict__ out, float* __restrict__ lse,
@@ -276,11 +239,10 @@ __global__ __launch_bounds__(256) void attn_qkv_fwd_bf16_kernel(const bf16_t* __
     constexpr int NBUF = LOOK + 1;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int per_xcd = gridDim.x >> 3;
-    const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int logical = xcd_tile(blockIdx.x, gridDim.x);
     if (logical >= total) return;
     const int b = logical / H, h = logical - b * H;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
+    const unsigned lds0 = lds_addr(smem);
 
     // this lane's share of a stage: 1-KiB pieces p = w + 4 i (i < 8); p < 8: token rows 8p .. 8p+7, else weight rows 8(p-8) ..
     const int prow = lane >> 3, pslot = lane & 7;
@@ -291,18 +253,18 @@ __global__ __launch_bounds__(256) void attn_qkv_fwd_bf16_kernel(const bf16_t* __
         if (p < 8) {
             const int row = 8 * p + prow;
             const int t = row < T ? row : T - 1;                          // rows past T: clamped here, zeroed in the images
-            const int f = (((row >> 1) & 1) << 2) | (((row >> 2) & 1) << 1) | ((row >> 3) & 1);
+            const int f = (((row >> 1) & 1) << 2) | (((row >> 2) & 1) << 1) | ((row >> 3) & 1);   // swz(row): see img_off
             src[i] = hin + ((size_t)b * T + t) * QA_C + ((pslot ^ f) << 3);
         } else {
             const int row = 8 * (p - 8) + prow;                           // 0..191: q rows, k rows, v rows of this head
-            const int f = (((row >> 1) & 1) << 2) | (((row >> 2) & 1) << 1) | ((row >> 3) & 1);
+            const int f = (((row >> 1) & 1) << 2) | (((row >> 2) & 1) << 1) | ((row >> 3) & 1);   // swz(row)
             src[i] = wqkv + ((size_t)(row >> 6) * H * HD + (size_t)h * HD + (row & 63)) * QA_C + ((pslot ^ f) << 3);
         }
     }
 #define GM3D_QA_STAGE(ST)                                                                        \
     {                                                                                            \
         const unsigned base = lds0 + ((ST) % NBUF) * QA_STAGE;                                   \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) qa_glds16(src[i] + (ST) * 64, base + 1024 * (w + 4 * i)); \
+        _Pragma("unroll") for (int i = 0; i < 8; ++i) glds16(src[i] + (ST) * 64, base + 1024 * (w + 4 * i)); \
     }
     f32x16 acc[3];
 #pragma unroll
@@ -324,7 +286,7 @@ __global__ __launch_bounds__(256) void attn_qkv_fwd_bf16_kernel(const bf16_t* __
         const unsigned char* ws = as + 64 * 128;                                                                            \
         _Pragma("unroll") for (int s = 0; s < 4; ++s) {                                                                     \
             const bf16x8 fa = img_row(as, wm + r, 2 * s + hh);                                                              \
-            _Pragma("unroll") for (int j = 0; j < 3; ++j) acc[j] = MFMA_BF16(img_row(ws, wn + 32 * j + r, 2 * s + hh), fa, acc[j]); \
+            _Pragma("unroll") for (int j = 0; j < 3; ++j) acc[j] = mfma_bf16(img_row(ws, wn + 32 * j + r, 2 * s + hh), fa, acc[j]); \
         }                                                                                                                   \
     }
     GM3D_QA_ITER(0) GM3D_QA_ITER(1) GM3D_QA_ITER(2) GM3D_QA_ITER(3) GM3D_QA_ITER(4) GM3D_QA_ITER(5)
@@ -528,8 +490,8 @@ __global__ __launch_bounds__(128 * NT) void attn_bwd_bf16_kernel(const bf16_t* _
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const int ch = 2 * ks + hh;
-                s = MFMA_BF16(img_row(Qi, 32 * qt + r, ch), img_row(Ki, key, ch), s);
-                dp = MFMA_BF16(img_row(Di, 32 * qt + r, ch), img_row(Vi, key, ch), dp);
+                s = mfma_bf16(img_row(Qi, 32 * qt + r, ch), img_row(Ki, key, ch), s);
+                dp = mfma_bf16(img_row(Di, 32 * qt + r, ch), img_row(Vi, key, ch), dp);
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
@@ -542,10 +504,10 @@ __global__ __launch_bounds__(128 * NT) void attn_bwd_bf16_kernel(const bf16_t* _
             for (int ks = 0; ks < 2; ++ks) {  // sum over q (X rows): M^T . X, M^T[i = d][k = q] by transposed reads
                 const bf16x8 pa = cvt8(s, ks, 1.0f);
                 const bf16x8 da = cvt8(dp, ks, scale);
-                x0 = MFMA_BF16(img_tr8(Di, 32 * qt, ks, hh, cb, lane), pa, x0);            // dV^T[d][key]
-                x1 = MFMA_BF16(img_tr8(Di, 32 * qt, ks, hh, 32 + cb, lane), pa, x1);
-                y0 = MFMA_BF16(img_tr8(Qi, 32 * qt, ks, hh, cb, lane), da, y0);            // dK^T[d][key]
-                y1 = MFMA_BF16(img_tr8(Qi, 32 * qt, ks, hh, 32 + cb, lane), da, y1);
+                x0 = mfma_bf16(img_tr8(Di, 32 * qt, ks, hh, cb, lane), pa, x0);            // dV^T[d][key]
+                x1 = mfma_bf16(img_tr8(Di, 32 * qt, ks, hh, 32 + cb, lane), pa, x1);
+                y0 = mfma_bf16(img_tr8(Qi, 32 * qt, ks, hh, cb, lane), da, y0);            // dK^T[d][key]
+                y1 = mfma_bf16(img_tr8(Qi, 32 * qt, ks, hh, 32 + cb, lane), da, y1);
             }
         }
     }
@@ -559,8 +521,8 @@ __global__ __launch_bounds__(128 * NT) void attn_bwd_bf16_kernel(const bf16_t* _
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const int ch = 2 * ks + hh;
-                s = MFMA_BF16(img_row(Ki, 32 * kt + r, ch), img_row(Qi, q, ch), s);
-                dp = MFMA_BF16(img_row(Vi, 32 * kt + r, ch), img_row(Di, q, ch), dp);
+                s = mfma_bf16(img_row(Ki, 32 * kt + r, ch), img_row(Qi, q, ch), s);
+                dp = mfma_bf16(img_row(Vi, 32 * kt + r, ch), img_row(Di, q, ch), dp);
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
@@ -571,8 +533,8 @@ __global__ __launch_bounds__(128 * NT) void attn_bwd_bf16_kernel(const bf16_t* _
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {  // sum over key: K^T . dS^T
                 const bf16x8 da = cvt8(dp, ks, scale);
-                x0 = MFMA_BF16(img_tr8(Ki, 32 * kt, ks, hh, cb, lane), da, x0);            // dQ^T[d][q]
-                x1 = MFMA_BF16(img_tr8(Ki, 32 * kt, ks, hh, 32 + cb, lane), da, x1);
+                x0 = mfma_bf16(img_tr8(Ki, 32 * kt, ks, hh, cb, lane), da, x0);            // dQ^T[d][q]
+                x1 = mfma_bf16(img_tr8(Ki, 32 * kt, ks, hh, 32 + cb, lane), da, x1);
             }
         }
     }
@@ -712,34 +674,24 @@ static int attn_check(const void* a, const void* b, int B, int T, int H, int dty
 
 }  // namespace gm3d
 
-template <class K, class... A>
-static int launch_attn(K kernel, int grid, int threads, size_t lds, hipStream_t st, A... args) {
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return GM3D_ELAUNCH;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, st, args...);
-    return hipGetLastError() == hipSuccess ? GM3D_OK : GM3D_ELAUNCH;
-}
-
 extern "C" int gm3d_attention_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, float scale,
                                   int dtype, gm3d_stream_t stream) {
     using namespace gm3d;
     int rc = attn_check(qkv, out, B, T, H, dtype);
     if (rc != GM3D_OK) return rc;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const int nt = (T + 31) / 32;
     if (dtype == GM3D_BF16) {
         const size_t lds = (size_t)3 * 32 * nt * 128;
-#define GM3D_AF(NT_) launch_attn(attn_fwd_bf16_kernel<NT_>, B * H, 64 * NT_, lds, st, (const bf16_t*)qkv, (bf16_t*)out, lse, T, H, scale)
+#define GM3D_AF(NT_) launch_lds<attn_fwd_bf16_kernel<NT_>>(dim3(B * H), dim3(64 * NT_), lds, stream, (const bf16_t*)qkv, (bf16_t*)out, lse, T, H, scale)
         return nt == 1 ? GM3D_AF(1) : nt == 2 ? GM3D_AF(2) : nt == 3 ? GM3D_AF(3) : GM3D_AF(4);
 #undef GM3D_AF
     }
     const int threads = 64 * nt;
     const int rows = T <= 64 ? 64 : 128;
     const size_t lds = sizeof(float) * 3 * rows * 64;
-    return T <= 64 ? launch_attn(attn_fwd_f32_kernel<2>, B * H, threads, lds, st, (const float*)qkv, (float*)out, lse, T, H, scale)
-                   : launch_attn(attn_fwd_f32_kernel<4>, B * H, threads, lds, st, (const float*)qkv, (float*)out, lse, T, H, scale);
+    return T <= 64 ? launch_lds<attn_fwd_f32_kernel<2>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv, (float*)out, lse, T, H, scale)
+                   : launch_lds<attn_fwd_f32_kernel<4>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv, (float*)out, lse, T, H, scale);
 }
 
 extern "C" int gm3d_attention_qkv_fwd(const void* h, const void* wqkv, void* out, float* lse, void* qkv_out, int B, int T, int H,
@@ -754,10 +706,9 @@ extern "C" int gm3d_attention_qkv_fwd(const void* h, const void* wqkv, void* out
     constexpr int LOOK = 1;
     const size_t lds = (size_t)(LOOK + 1) * QA_STAGE;
     const int total = B * H, grid = (total + 7) / 8 * 8;
-    hipStream_t st = (hipStream_t)stream;
-    return qkv_out ? launch_attn(attn_qkv_fwd_bf16_kernel<LOOK, true>, grid, 256, lds, st, (const bf16_t*)h, (const bf16_t*)wqkv,
+    return qkv_out ? launch_lds<attn_qkv_fwd_bf16_kernel<LOOK, true>>(dim3(grid), dim3(256), lds, stream, (const bf16_t*)h, (const bf16_t*)wqkv,
                                  (bf16_t*)out, lse, (bf16_t*)qkv_out, T, H, scale, total)
-                   : launch_attn(attn_qkv_fwd_bf16_kernel<LOOK, false>, grid, 256, lds, st, (const bf16_t*)h, (const bf16_t*)wqkv,
+                   : launch_lds<attn_qkv_fwd_bf16_kernel<LOOK, false>>(dim3(grid), dim3(256), lds, stream, (const bf16_t*)h, (const bf16_t*)wqkv,
                                  (bf16_t*)out, lse, (bf16_t*)nullptr, T, H, scale, total);
 }
 
@@ -768,12 +719,11 @@ extern "C" int gm3d_attention_bwd(const void* qkv, const void* out, const void* 
     if (rc != GM3D_OK) return rc;
     if (!dout || !lse || !dqkv) return GM3D_EINVAL;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const int nt = (T + 31) / 32;
     if (dtype == GM3D_BF16) {
         const size_t lds = (size_t)4 * 32 * nt * 128 + 2 * 32 * nt * sizeof(float);
 #define GM3D_AB(NT_)                                                                                                      \
-    launch_attn(attn_bwd_bf16_kernel<NT_>, B * H, 128 * NT_, lds, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, \
+    launch_lds<attn_bwd_bf16_kernel<NT_>>(dim3(B * H), dim3(128 * NT_), lds, stream, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, \
                 (bf16_t*)dqkv, T, H, scale)
         return nt == 1 ? GM3D_AB(1) : nt == 2 ? GM3D_AB(2) : nt == 3 ? GM3D_AB(3) : GM3D_AB(4);
 #undef GM3D_AB
@@ -781,8 +731,8 @@ extern "C" int gm3d_attention_bwd(const void* qkv, const void* out, const void* 
     const int threads = 128 * nt;   // NT key-tile waves + NT query-tile waves
     const int rows = T <= 64 ? 64 : 128;
     const size_t lds = sizeof(float) * (4 * rows * 64 + 2 * rows);
-    return T <= 64 ? launch_attn(attn_bwd_f32_kernel<2>, B * H, threads, lds, st, (const float*)qkv, (const float*)out,
+    return T <= 64 ? launch_lds<attn_bwd_f32_kernel<2>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv, (const float*)out,
                                  (const float*)dout, lse, (float*)dqkv, T, H, scale)
-                   : launch_attn(attn_bwd_f32_kernel<4>, B * H, threads, lds, st, (const float*)qkv, (const float*)out,
+                   : launch_lds<attn_bwd_f32_kernel<4>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv, (const float*)out,
                                  (const float*)dout, lse, (float*)dqkv, T, H, scale);
 }

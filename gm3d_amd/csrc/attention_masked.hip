@@ -15,53 +15,26 @@
 // operand straight from the accumulators, V^T / Q^T / dO^T / K^T fragments come out of row-major LDS images by
 // ds_read_b64_tr_b16.  K and V (forward) or Q, K, V, dO (backward) of the whole head sit in LDS (<= 512 x 64 bf16 each).
 // f32 (parity mode): plain one-thread-per-query / one-thread-per-key kernels -- exact fp32 dot products in a fixed order.
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace gm3d {
-
-typedef __bf16 mbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 mbf16x4 __attribute__((ext_vector_type(4)));
-typedef float mf32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) mbf16x4 lds_mbf16x4;
-
-#define MMFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
-
-__device__ __forceinline__ int mcrow(int g, int hh) { return (g & 3) + 8 * (g >> 2) + 4 * hh; }
-__device__ __forceinline__ mf32x16 mzero16() {
-    mf32x16 z;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) z[g] = 0.f;
-    return z;
-}
-__device__ __forceinline__ mbf16x8 mzero8() {
-    mbf16x8 z;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z[j] = (bf16_t)0.0f;
-    return z;
-}
-__device__ __forceinline__ mbf16x8 mcvt8(const mf32x16& x, int s, float mul) {
-    mbf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (bf16_t)(x[8 * s + j] * mul);
-    return v;
-}
 
 // LDS image of a (rows, HD) bf16 matrix: row pitch HD*2 + 16 bytes (48 / 80 / 144: 16-byte row reads of 16 consecutive rows hit
 // 16 different bank quads; transposed reads are at worst 2-way)
 template <int HD> struct MImg {
     static constexpr int PITCH = HD * 2 + 16;
-    static __device__ __forceinline__ mbf16x8 row(const unsigned char* img, int r, int ch) {     // 8 consecutive d starting at 8*ch
-        return *reinterpret_cast<const mbf16x8*>(img + r * PITCH + ch * 16);
+    static __device__ __forceinline__ bf16x8 row(const unsigned char* img, int r, int ch) {     // 8 consecutive d starting at 8*ch
+        return *reinterpret_cast<const bf16x8*>(img + r * PITCH + ch * 16);
     }
     // fragment A[i = column][k] in accumulator-as-operand k order: rows k0 + 16 s + 4 hh + {0..3, 8..11}, column colblk + (lane&15)
-    static __device__ __forceinline__ mbf16x8 tr8(const unsigned char* img, int k0, int s, int hh, int colblk, int lane) {
+    static __device__ __forceinline__ bf16x8 tr8(const unsigned char* img, int k0, int s, int hh, int colblk, int lane) {
         const int l16 = lane & 15, q = l16 >> 2, p = l16 & 3;
         int col = colblk + 4 * p;
         if (col >= HD) col -= HD * (col / HD);            // lanes past the head dim read valid (ignored) data: pad, don't mask
         const int r0 = k0 + 16 * s + 4 * hh + q;
-        const mbf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_mbf16x4*)(img + r0 * PITCH + col * 2));
-        const mbf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_mbf16x4*)(img + (r0 + 8) * PITCH + col * 2));
-        mbf16x8 v;
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(img + r0 * PITCH + col * 2));
+        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(img + (r0 + 8) * PITCH + col * 2));
+        bf16x8 v;
 #pragma unroll
         for (int j = 0; j < 4; ++j) { v[j] = lo[j]; v[4 + j] = hi[j]; }
         return v;
@@ -132,13 +105,13 @@ __global__ __launch_bounds__(64 * NWV) void mattn_fwd_bf16_kernel(const bf16_t* 
     if (q0 + 32 * w >= T) return;                   // whole tile past the end (wave-uniform)
     const bool q_ok = q < T;
     const unsigned* mrow = mask ? mask + ((size_t)b * T + (q_ok ? q : 0)) * W : nullptr;
-    mbf16x8 fq[KS];
+    bf16x8 fq[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) fq[s] = I::row(Qi, 32 * w + r, 2 * s + hh);
     float m = -INFINITY, l = 0.f;
-    mf32x16 o[DT];
+    f32x16 o[DT];
 #pragma unroll
-    for (int d = 0; d < DT; ++d) o[d] = mzero16();
+    for (int d = 0; d < DT; ++d) o[d] = zero16();
     const int cb = 16 * ((lane >> 4) & 1);
     for (int kt = 0; kt < NK; ++kt) {
         // a key tile that is blocked for every query of this wave's tile contributes exp(-inf) = 0 to every sum and leaves the
@@ -146,13 +119,13 @@ __global__ __launch_bounds__(64 * NWV) void mattn_fwd_bf16_kernel(const bf16_t* 
         // (gm3d_partition_visible) the filler rows behind them form such tiles, as keys and as queries.
         const unsigned mw = mask_word(mrow, q_ok, kt, T);
         if (__ballot(mw != 0xffffffffu) == 0ull) continue;
-        mf32x16 st = mzero16();
+        f32x16 st = zero16();
 #pragma unroll
-        for (int s = 0; s < KS; ++s) st = MMFMA(I::row(Ki, 32 * kt + r, 2 * s + hh), fq[s], st);
+        for (int s = 0; s < KS; ++s) st = mfma_bf16(I::row(Ki, 32 * kt + r, 2 * s + hh), fq[s], st);
         float tm = -INFINITY;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-            st[g] = ((mw >> mcrow(g, hh)) & 1u) ? -INFINITY : st[g] * scale;
+            st[g] = ((mw >> crow(g, hh)) & 1u) ? -INFINITY : st[g] * scale;
             tm = fmaxf(tm, st[g]);
         }
         tm = fmaxf(tm, __shfl_xor(tm, 32));
@@ -173,9 +146,9 @@ __global__ __launch_bounds__(64 * NWV) void mattn_fwd_bf16_kernel(const bf16_t* 
             for (int g = 0; g < 16; ++g) o[d][g] *= alpha;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const mbf16x8 p = mcvt8(st, s, 1.0f);
+            const bf16x8 p = cvt8(st, s, 1.0f);
 #pragma unroll
-            for (int d = 0; d < DT; ++d) o[d] = MMFMA(I::tr8(Vi, 32 * kt, s, hh, 32 * d + cb, lane), p, o[d]);
+            for (int d = 0; d < DT; ++d) o[d] = mfma_bf16(I::tr8(Vi, 32 * kt, s, hh, 32 * d + cb, lane), p, o[d]);
         }
     }
     const float inv = l > 0.f ? 1.0f / l : 0.f;
@@ -187,10 +160,10 @@ __global__ __launch_bounds__(64 * NWV) void mattn_fwd_bf16_kernel(const bf16_t* 
             for (int g4 = 0; g4 < 4; ++g4) {
                 const int d0 = 32 * d + 8 * g4 + 4 * hh;
                 if (d0 < HD) {
-                    mbf16x4 pk;
+                    bf16x4 pk;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) pk[e] = (bf16_t)(o[d][4 * g4 + e] * inv);
-                    *reinterpret_cast<mbf16x4*>(og + d0) = pk;
+                    *reinterpret_cast<bf16x4*>(og + d0) = pk;
                 }
             }
         if (hh == 0) lse[((size_t)b * H + h) * T + q] = l > 0.f ? m + logf(l) : 0.f;
@@ -235,8 +208,8 @@ __global__ __launch_bounds__(128 * NTP) void mattn_bwd_bf16_kernel(const bf16_t*
         if (i < T) {
 #pragma unroll
             for (int c = 0; c < HD / 8; ++c) {
-                const mbf16x8 o8 = *reinterpret_cast<const mbf16x8*>(Og + (size_t)i * os + c * 8);
-                const mbf16x8 d8 = *reinterpret_cast<const mbf16x8*>(Dg + (size_t)i * os + c * 8);
+                const bf16x8 o8 = *reinterpret_cast<const bf16x8*>(Og + (size_t)i * os + c * 8);
+                const bf16x8 d8 = *reinterpret_cast<const bf16x8*>(Dg + (size_t)i * os + c * 8);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc += (float)o8[j] * (float)d8[j];
             }
@@ -252,65 +225,65 @@ __global__ __launch_bounds__(128 * NTP) void mattn_bwd_bf16_kernel(const bf16_t*
     const int row = 32 * tile + r;                  // this lane's key (waves 0..3) or query (waves 4..7)
     const bool row_ok = row < T;
     const unsigned* mrow = mask ? mask + ((size_t)b * T + (row_ok ? row : 0)) * W : nullptr;
-    mf32x16 x[DT], y[DT];
+    f32x16 x[DT], y[DT];
 #pragma unroll
-    for (int d = 0; d < DT; ++d) { x[d] = mzero16(); y[d] = mzero16(); }
+    for (int d = 0; d < DT; ++d) { x[d] = zero16(); y[d] = zero16(); }
     if (w < NTP) {
         // phase A: X[q][key] tiles (rows = q in registers, cols = key on the lane); the mask is symmetric: row `key`, word qt
-        mbf16x8 fk[KS], fv[KS];
+        bf16x8 fk[KS], fv[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) { fk[s] = I::row(Ki, row, 2 * s + hh); fv[s] = I::row(Vi, row, 2 * s + hh); }
         for (int qt = 0; qt < NT; ++qt) {
             const unsigned mw = mask_word(mrow, row_ok, qt, T);
             if (__ballot(mw != 0xffffffffu) == 0ull) continue;        // every pair of this tile blocked: p = 0 throughout (exact)
-            mf32x16 s = mzero16(), dp = mzero16();
+            f32x16 s = zero16(), dp = zero16();
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                s = MMFMA(I::row(Qi, 32 * qt + r, 2 * ks + hh), fk[ks], s);
-                dp = MMFMA(I::row(Di, 32 * qt + r, 2 * ks + hh), fv[ks], dp);
+                s = mfma_bf16(I::row(Qi, 32 * qt + r, 2 * ks + hh), fk[ks], s);
+                dp = mfma_bf16(I::row(Di, 32 * qt + r, 2 * ks + hh), fv[ks], dp);
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const int q = 32 * qt + mcrow(g, hh);
-                const float p = ((mw >> mcrow(g, hh)) & 1u) ? 0.f : __expf(s[g] * scale - Ls[q]);
+                const int q = 32 * qt + crow(g, hh);
+                const float p = ((mw >> crow(g, hh)) & 1u) ? 0.f : __expf(s[g] * scale - Ls[q]);
                 s[g] = p;
                 dp[g] = p * (dp[g] - Del[q]);
             }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const mbf16x8 pa = mcvt8(s, ks, 1.0f), da = mcvt8(dp, ks, scale);
+                const bf16x8 pa = cvt8(s, ks, 1.0f), da = cvt8(dp, ks, scale);
 #pragma unroll
                 for (int d = 0; d < DT; ++d) {
-                    x[d] = MMFMA(I::tr8(Di, 32 * qt, ks, hh, 32 * d + cb, lane), pa, x[d]);      // dV^T[d][key]
-                    y[d] = MMFMA(I::tr8(Qi, 32 * qt, ks, hh, 32 * d + cb, lane), da, y[d]);      // dK^T[d][key]
+                    x[d] = mfma_bf16(I::tr8(Di, 32 * qt, ks, hh, 32 * d + cb, lane), pa, x[d]);      // dV^T[d][key]
+                    y[d] = mfma_bf16(I::tr8(Qi, 32 * qt, ks, hh, 32 * d + cb, lane), da, y[d]);      // dK^T[d][key]
                 }
             }
         }
     } else {
         // phase B: X'[key][q] tiles (rows = key in registers, cols = q on the lane)
-        mbf16x8 fq[KS], fd[KS];
+        bf16x8 fq[KS], fd[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) { fq[s] = I::row(Qi, row, 2 * s + hh); fd[s] = I::row(Di, row, 2 * s + hh); }
         const float lq = Ls[row], dq_ = Del[row];
         for (int kt = 0; kt < NT; ++kt) {
             const unsigned mw = mask_word(mrow, row_ok, kt, T);
             if (__ballot(mw != 0xffffffffu) == 0ull) continue;
-            mf32x16 s = mzero16(), dp = mzero16();
+            f32x16 s = zero16(), dp = zero16();
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                s = MMFMA(I::row(Ki, 32 * kt + r, 2 * ks + hh), fq[ks], s);
-                dp = MMFMA(I::row(Vi, 32 * kt + r, 2 * ks + hh), fd[ks], dp);
+                s = mfma_bf16(I::row(Ki, 32 * kt + r, 2 * ks + hh), fq[ks], s);
+                dp = mfma_bf16(I::row(Vi, 32 * kt + r, 2 * ks + hh), fd[ks], dp);
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const float p = ((mw >> mcrow(g, hh)) & 1u) ? 0.f : __expf(s[g] * scale - lq);
+                const float p = ((mw >> crow(g, hh)) & 1u) ? 0.f : __expf(s[g] * scale - lq);
                 dp[g] = p * (dp[g] - dq_);
             }
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const mbf16x8 da = mcvt8(dp, ks, scale);
+                const bf16x8 da = cvt8(dp, ks, scale);
 #pragma unroll
-                for (int d = 0; d < DT; ++d) x[d] = MMFMA(I::tr8(Ki, 32 * kt, ks, hh, 32 * d + cb, lane), da, x[d]);   // dQ^T[d][q]
+                for (int d = 0; d < DT; ++d) x[d] = mfma_bf16(I::tr8(Ki, 32 * kt, ks, hh, 32 * d + cb, lane), da, x[d]);   // dQ^T[d][q]
             }
         }
     }
@@ -323,11 +296,11 @@ __global__ __launch_bounds__(128 * NTP) void mattn_bwd_bf16_kernel(const bf16_t*
             for (int g4 = 0; g4 < 4; ++g4) {
                 const int d0 = 32 * d + 8 * g4 + 4 * hh;
                 if (d0 < HD) {
-                    mbf16x4 pk, pk2;
+                    bf16x4 pk, pk2;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { pk[e] = (bf16_t)x[d][4 * g4 + e]; pk2[e] = (bf16_t)y[d][4 * g4 + e]; }
-                    *reinterpret_cast<mbf16x4*>(g0 + d0) = pk;
-                    if (w < NTP) *reinterpret_cast<mbf16x4*>(g1 + d0) = pk2;
+                    *reinterpret_cast<bf16x4*>(g0 + d0) = pk;
+                    if (w < NTP) *reinterpret_cast<bf16x4*>(g1 + d0) = pk2;
                 }
             }
     }
@@ -502,14 +475,6 @@ static int mattn_check(const void* a, const void* b, int B, int T, int H, int HD
     return GM3D_OK;
 }
 
-template <class K>
-static int mattn_attr(K kernel, size_t lds) {
-    if (lds > 160 * 1024) return GM3D_EUNSUPPORTED;
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return GM3D_ELAUNCH;
-    return GM3D_OK;
-}
-
 }  // namespace gm3d
 
 extern "C" int gm3d_attention_masked_set_wide(int on) {
@@ -532,14 +497,8 @@ extern "C" int gm3d_radius_mask_bits_m(const float* center, const unsigned char*
     const int W = (G + 31) / 32;
     if (G > 8192 || B > 65535) return GM3D_EUNSUPPORTED;
     const size_t lds = (size_t)4 * G * sizeof(float);       // G > 4096: above the 64 KiB default, up to 128 KiB at G = 8192
-    if (lds > 64 * 1024) {
-        static LdsAttr attr;
-        if (!attr.ensure((const void*)radius_mask_bits_kernel, lds)) return GM3D_ELAUNCH;
-    }
-    hipLaunchKernelGGL(radius_mask_bits_kernel, dim3((unsigned)((G * W + 255) / 256), (unsigned)B), dim3(256), lds, (hipStream_t)stream,
-                       center, vis, radius, B, G, W, bits, inv);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<radius_mask_bits_kernel>(dim3((unsigned)((G * W + 255) / 256), (unsigned)B), dim3(256), lds, stream, center, vis,
+                                               radius, B, G, W, bits, inv);
 }
 
 extern "C" int gm3d_attention_masked_fwd(const void* qkv, const unsigned* mask, void* out, float* lse, int B, int T, int H, int HD,
@@ -549,33 +508,25 @@ extern "C" int gm3d_attention_masked_fwd(const void* qkv, const unsigned* mask, 
     if (rc != GM3D_OK) return rc;
     if (!lse) return GM3D_EINVAL;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const int W = (T + 31) / 32;
     if (dtype == GM3D_BF16) {
         const int rowsK = 32 * W;
         const int nwv = (HD <= 32 && T > 128 && MATTN_WIDE) ? 8 : 4;          // query tiles (= waves) per workgroup
         const size_t lds = (size_t)(2 * rowsK + 32 * nwv) * (HD * 2 + 16);
         const dim3 grid(B * H, (T + 32 * nwv - 1) / (32 * nwv));
-#define GM3D_MF(HD_, NWV_)                                                                                             \
-    {                                                                                                                  \
-        rc = mattn_attr(mattn_fwd_bf16_kernel<HD_, NWV_>, lds);                                                        \
-        if (rc != GM3D_OK) return rc;                                                                                  \
-        hipLaunchKernelGGL((mattn_fwd_bf16_kernel<HD_, NWV_>), grid, dim3(64 * NWV_), lds, st, (const bf16_t*)qkv, mask, (bf16_t*)out, lse, \
-                           T, H, W, scale);                                                                           \
-    }
-        if (HD == 16) { if (nwv == 8) GM3D_MF(16, 8) else GM3D_MF(16, 4) }
-        else if (HD == 32) { if (nwv == 8) GM3D_MF(32, 8) else GM3D_MF(32, 4) }
-        else GM3D_MF(64, 4)
-#undef GM3D_MF
-    } else {
-        const long long n = (long long)B * H * T;
-        const dim3 grid((unsigned)((n + 127) / 128));
-#define GM3D_MF(HD_) hipLaunchKernelGGL(mattn_fwd_f32_kernel<HD_>, grid, dim3(128), 0, st, (const float*)qkv, mask, (float*)out, lse, B, T, H, W, scale);
-        if (HD == 16) GM3D_MF(16) else if (HD == 32) GM3D_MF(32) else GM3D_MF(64)
+#define GM3D_MF(HD_, NWV_)                                                                                                         \
+    launch_lds<mattn_fwd_bf16_kernel<HD_, NWV_>>(grid, dim3(64 * NWV_), lds, stream, (const bf16_t*)qkv, mask, (bf16_t*)out, lse, T, H, W, \
+                                                 scale)
+        if (HD == 16) return nwv == 8 ? GM3D_MF(16, 8) : GM3D_MF(16, 4);
+        if (HD == 32) return nwv == 8 ? GM3D_MF(32, 8) : GM3D_MF(32, 4);
+        return GM3D_MF(64, 4);
 #undef GM3D_MF
     }
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    const long long n = (long long)B * H * T;
+    const dim3 grid((unsigned)((n + 127) / 128));
+#define GM3D_MF(HD_) launch_lds<mattn_fwd_f32_kernel<HD_>>(grid, dim3(128), 0, stream, (const float*)qkv, mask, (float*)out, lse, B, T, H, W, scale)
+    return HD == 16 ? GM3D_MF(16) : HD == 32 ? GM3D_MF(32) : GM3D_MF(64);
+#undef GM3D_MF
 }
 
 extern "C" int gm3d_attention_masked_bwd(const void* qkv, const unsigned* mask, const void* out, const void* dout, const float* lse,
@@ -585,31 +536,25 @@ extern "C" int gm3d_attention_masked_bwd(const void* qkv, const unsigned* mask, 
     if (rc != GM3D_OK) return rc;
     if (!dout || !lse || !dqkv) return GM3D_EINVAL;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const int W = (T + 31) / 32;
     if (dtype == GM3D_BF16) {
         const int rows = 32 * W;
         const size_t lds = (size_t)4 * rows * (HD * 2 + 16) + (size_t)2 * rows * sizeof(float);
         const int ntp = (HD <= 32 && T > 128 && MATTN_WIDE) ? 8 : 4;          // key tiles (= query tiles) per workgroup
         const dim3 grid(B * H, (T + 32 * ntp - 1) / (32 * ntp));
-#define GM3D_MB(HD_, NTP_)                                                                                             \
-    {                                                                                                                  \
-        rc = mattn_attr(mattn_bwd_bf16_kernel<HD_, NTP_>, lds);                                                        \
-        if (rc != GM3D_OK) return rc;                                                                                  \
-        hipLaunchKernelGGL((mattn_bwd_bf16_kernel<HD_, NTP_>), grid, dim3(128 * NTP_), lds, st, (const bf16_t*)qkv, mask, (const bf16_t*)out, \
-                           (const bf16_t*)dout, lse, (bf16_t*)dqkv, T, H, W, scale);                                  \
-    }
-        if (HD == 16) { if (ntp == 8) GM3D_MB(16, 8) else GM3D_MB(16, 4) }
-        else if (HD == 32) { if (ntp == 8) GM3D_MB(32, 8) else GM3D_MB(32, 4) }
-        else GM3D_MB(64, 4)
-#undef GM3D_MB
-    } else {
-        const long long n = (long long)B * H * T;
-        const dim3 grid((unsigned)((n + 127) / 128), 2);
-#define GM3D_MB(HD_) hipLaunchKernelGGL(mattn_bwd_f32_kernel<HD_>, grid, dim3(128), 0, st, (const float*)qkv, mask, (const float*)out, (const float*)dout, lse, (float*)dqkv, B, T, H, W, scale);
-        if (HD == 16) GM3D_MB(16) else if (HD == 32) GM3D_MB(32) else GM3D_MB(64)
+#define GM3D_MB(HD_, NTP_)                                                                                                         \
+    launch_lds<mattn_bwd_bf16_kernel<HD_, NTP_>>(grid, dim3(128 * NTP_), lds, stream, (const bf16_t*)qkv, mask, (const bf16_t*)out,        \
+                                                 (const bf16_t*)dout, lse, (bf16_t*)dqkv, T, H, W, scale)
+        if (HD == 16) return ntp == 8 ? GM3D_MB(16, 8) : GM3D_MB(16, 4);
+        if (HD == 32) return ntp == 8 ? GM3D_MB(32, 8) : GM3D_MB(32, 4);
+        return GM3D_MB(64, 4);
 #undef GM3D_MB
     }
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    const long long n = (long long)B * H * T;
+    const dim3 grid((unsigned)((n + 127) / 128), 2);
+#define GM3D_MB(HD_)                                                                                                                \
+    launch_lds<mattn_bwd_f32_kernel<HD_>>(grid, dim3(128), 0, stream, (const float*)qkv, mask, (const float*)out, (const float*)dout, lse, \
+                                          (float*)dqkv, B, T, H, W, scale)
+    return HD == 16 ? GM3D_MB(16) : HD == 32 ? GM3D_MB(32) : GM3D_MB(64);
+#undef GM3D_MB
 }

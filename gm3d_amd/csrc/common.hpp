@@ -15,10 +15,10 @@
 
 namespace gm3d {
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: one static instance per launch site
-// remembers, per device ordinal, how many bytes were granted (a process that launches on a second device, or two threads
-// racing through the first launch, set it again instead of skipping it).  hipGetDevice is thread-local and capture-safe.
-struct LdsAttr {
+// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: lds_grant<Kernel> remembers, per device
+// ordinal, how many bytes were granted (a process that launches on a second device, or two threads racing through the first
+// launch, set it again instead of skipping it).  hipGetDevice is thread-local and capture-safe.
+struct LdsGrant {
     std::atomic<int> granted[32];
     bool ensure(const void* fn, size_t lds) {
         int dev = 0;
@@ -30,6 +30,20 @@ struct LdsAttr {
         return true;
     }
 };
+template <auto Kernel> LdsGrant lds_grant;      // one per kernel (keyed on the kernel itself, not on its signature)
+
+constexpr size_t GM3D_LDS_DEFAULT = 48 * 1024, GM3D_LDS_MAX = 160 * 1024;
+
+// Launches Kernel<<<grid, block, lds, stream>>>(args...) and checks the launch.  More than the CU's 160 KiB of LDS is refused before
+// any HIP call (GM3D_EUNSUPPORTED); above 48 KiB the kernel's per-device LDS limit is raised first (once per kernel and device).
+template <auto Kernel, class... Args>
+int launch_lds(dim3 grid, dim3 block, size_t lds, gm3d_stream_t stream, Args... args) {
+    if (lds > GM3D_LDS_MAX) return GM3D_EUNSUPPORTED;
+    if (lds > GM3D_LDS_DEFAULT && !lds_grant<Kernel>.ensure((const void*)Kernel, lds)) return GM3D_ELAUNCH;
+    hipLaunchKernelGGL(Kernel, grid, block, lds, (hipStream_t)stream, args...);
+    GM3D_CHECK_LAUNCH();
+    return GM3D_OK;
+}
 
 // Squared distance with the evaluation order fixed by the oracle contract
 // ((dx*dx + dy*dy) + dz*dz, fp32, no FMA).  The translation unit is compiled with

@@ -11,13 +11,10 @@
 // double-buffered LDS stages with ONE barrier per stage, v_mfma_f32_32x32x16_bf16 with the output computed transposed
 // (lanes = rows of C, registers = 4 consecutive columns) and an LDS-staged epilogue that adds the bias in fp32 and
 // writes 16-byte row-contiguous pieces.
-#include "common.hpp"
+#include "mfma.hpp"
 #include <stdlib.h>
 
 namespace gm3d {
-
-typedef __bf16 gbf16x8 __attribute__((ext_vector_type(8)));
-typedef float gf32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GBM = 128, GBN = 128, GBK = 64;
 constexpr int GPITCH = 72;                     // bf16 elements per LDS row (64 + 8 pad: conflict-free 16-byte operand reads)
@@ -51,11 +48,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const bf16_t* __re
     bf16_t* sm = reinterpret_cast<bf16_t*>(gsm);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r = lane & 31, hh = lane >> 5;
-    // XCD-aware tile order: the hardware deals workgroups round-robin over the 8 XCDs (each with its own L2), so workgroup b
-    // takes logical tile (b % 8) * per_xcd + b / 8 -- every XCD walks a contiguous run of tiles in (tile_m, tile_n) order and
-    // the tiles_n workgroups that share one block of A rows hit the same L2 (A comes from HBM once, not tiles_n times).
-    const int per_xcd = gridDim.x >> 3;
-    const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    // XCD-aware tile order: every XCD walks a contiguous run of tiles in (tile_m, tile_n) order, so the tiles_n workgroups that
+    // share one block of A rows hit the same L2 (A comes from HBM once, not tiles_n times).
+    const int logical = xcd_tile(blockIdx.x, gridDim.x);
     if (logical >= total_tiles) return;
     const int tile_m = logical / tiles_n, tile_n = logical - tile_m * tiles_n;
     constexpr int BM = 64 * WMI, ACH = 2 * WMI;           // tile rows; 16-byte A chunks per thread per stage
@@ -66,7 +61,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const bf16_t* __re
     // global -> register prefetch, TWO stages deep: 4 chunks of A and 4 of W per thread per stage (16 bytes each), two register
     // sets.  Iteration kt issues the loads of stage kt+2, multiplies stage kt, and only then parks stage kt+1 (issued one
     // iteration ago) in the LDS buffer that stage kt-1 vacated: a load has a whole iteration plus a multiply to arrive.
-    gbf16x8 pa[2][ACH], pw[2][4];
+    bf16x8 pa[2][ACH], pw[2][4];
     float4 pg[2][2], pb[2][2];                                // LNA: the gamma / beta chunk of the stage
     float mu[ACH], rsd[ACH];
     const int crow = tid >> 3, ckc = (tid & 7) * 8;           // chunk c = tid + 256*i -> row = crow + 32*i, k offset ckc
@@ -105,8 +100,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const bf16_t* __re
 #define GM3D_LOAD_STAGE(SET, K0)                                                          \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                       \
         const int ko_ = (RAG && dead && (K0) == klast) ? kredir : (K0);                   \
-        if (i < ACH) pa[SET][i] = *reinterpret_cast<const gbf16x8*>(A + aoff[i] + ko_);   \
-        pw[SET][i] = *reinterpret_cast<const gbf16x8*>(W + woff[i] + ko_);                \
+        if (i < ACH) pa[SET][i] = *reinterpret_cast<const bf16x8*>(A + aoff[i] + ko_);    \
+        pw[SET][i] = *reinterpret_cast<const bf16x8*>(W + woff[i] + ko_);                 \
     }                                                                                     \
     if (LNA) {                                                                            \
         pg[SET][0] = *reinterpret_cast<const float4*>(gamma + ckc + (K0));                \
@@ -122,10 +117,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const bf16_t* __re
             const int row = crow + 32 * i;                                                \
             if (i < ACH) {                                                                \
                 if (LNA) {                                                                \
-                    const gbf16x8 xv = pa[SET][i];                                        \
+                    const bf16x8 xv = pa[SET][i];                                         \
                     const float4 g0 = pg[SET][0], g1 = pg[SET][1], b0 = pb[SET][0], b1 = pb[SET][1];      \
                     const float m_ = mu[i], r_ = rsd[i];                                  \
-                    gbf16x8 hv;                                                           \
+                    bf16x8 hv;                                                            \
                     hv[0] = (bf16_t)(((float)xv[0] - m_) * r_ * g0.x + b0.x);             \
                     hv[1] = (bf16_t)(((float)xv[1] - m_) * r_ * g0.y + b0.y);             \
                     hv[2] = (bf16_t)(((float)xv[2] - m_) * r_ * g0.z + b0.z);             \
@@ -134,26 +129,26 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const bf16_t* __re
                     hv[5] = (bf16_t)(((float)xv[5] - m_) * r_ * g1.y + b1.y);             \
                     hv[6] = (bf16_t)(((float)xv[6] - m_) * r_ * g1.z + b1.z);             \
                     hv[7] = (bf16_t)(((float)xv[7] - m_) * r_ * g1.w + b1.w);             \
-                    *reinterpret_cast<gbf16x8*>(as_ + row * GPITCH + ckc) = hv;           \
+                    *reinterpret_cast<bf16x8*>(as_ + row * GPITCH + ckc) = hv;            \
                     if (Hout && tile_n == 0 && m0 + row < M)                              \
-                        *reinterpret_cast<gbf16x8*>(Hout + (size_t)(m0 + row) * K + (K0) + ckc) = hv;     \
+                        *reinterpret_cast<bf16x8*>(Hout + (size_t)(m0 + row) * K + (K0) + ckc) = hv;     \
                 } else if (RAG && dead && (K0) == klast) {                                \
-                    gbf16x8 z_;                                                           \
+                    bf16x8 z_;                                                            \
                     _Pragma("unroll") for (int e = 0; e < 8; ++e) z_[e] = (bf16_t)0.f;    \
-                    *reinterpret_cast<gbf16x8*>(as_ + row * GPITCH + ckc) = z_;           \
+                    *reinterpret_cast<bf16x8*>(as_ + row * GPITCH + ckc) = z_;            \
                 } else                                                                    \
-                    *reinterpret_cast<gbf16x8*>(as_ + row * GPITCH + ckc) = pa[SET][i];   \
+                    *reinterpret_cast<bf16x8*>(as_ + row * GPITCH + ckc) = pa[SET][i];    \
             }                                                                             \
             if (RAG && dead && (K0) == klast) {                                           \
-                gbf16x8 z_;                                                               \
+                bf16x8 z_;                                                                \
                 _Pragma("unroll") for (int e = 0; e < 8; ++e) z_[e] = (bf16_t)0.f;        \
-                *reinterpret_cast<gbf16x8*>(ws_ + row * GPITCH + ckc) = z_;               \
+                *reinterpret_cast<bf16x8*>(ws_ + row * GPITCH + ckc) = z_;                \
             } else                                                                        \
-                *reinterpret_cast<gbf16x8*>(ws_ + row * GPITCH + ckc) = pw[SET][i];       \
+                *reinterpret_cast<bf16x8*>(ws_ + row * GPITCH + ckc) = pw[SET][i];        \
         }                                                                                 \
     }
 
-    gf32x16 acc[WMI][2];
+    f32x16 acc[WMI][2];
 #pragma unroll
     for (int i = 0; i < WMI; ++i)
 #pragma unroll
@@ -177,20 +172,20 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_bf16_kernel(const bf16_t* __re
         const bf16_t* ws = as + BM * GPITCH;                                                                               \
         /* all 16 operand fragments of the stage are requested from LDS before the first MFMA: one LDS round trip per */   \
         /* stage on the critical path instead of one per k-step (the compiler then drains lgkmcnt progressively)       */   \
-        gbf16x8 fa[4][WMI], fw[4][2];                                                                                      \
+        bf16x8 fa[4][WMI], fw[4][2];                                                                                        \
         _Pragma("unroll") for (int s = 0; s < 4; ++s) {                                                                    \
             const int ko = 16 * s + 8 * hh;                                                                                \
             _Pragma("unroll") for (int i = 0; i < WMI; ++i)                                                                \
-                fa[s][i] = *reinterpret_cast<const gbf16x8*>(as + (wm + 32 * i + r) * GPITCH + ko);                        \
+                fa[s][i] = *reinterpret_cast<const bf16x8*>(as + (wm + 32 * i + r) * GPITCH + ko);                         \
             _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                  \
-                fw[s][j] = *reinterpret_cast<const gbf16x8*>(ws + (wn + 32 * j + r) * GPITCH + ko);                        \
+                fw[s][j] = *reinterpret_cast<const bf16x8*>(ws + (wn + 32 * j + r) * GPITCH + ko);                         \
         }                                                                                                                  \
         __builtin_amdgcn_sched_barrier(0);   /* keep the scheduler from sinking the reads back between the MFMAs */        \
         /* transposed product: rows (registers) = n, columns (lanes) = m */                                                \
         _Pragma("unroll") for (int s = 0; s < 4; ++s)                                                                      \
             _Pragma("unroll") for (int i = 0; i < WMI; ++i)                                                                \
                 _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                              \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[s][j], fa[s][i], acc[i][j], 0, 0, 0);           \
+                    acc[i][j] = mfma_bf16(fw[s][j], fa[s][i], acc[i][j]);                                                  \
         if ((KT_) + 1 < KT) GM3D_STORE_STAGE(NXT, NXT, ((KT_) + 1) * GBK)   /* stage KT_+1 (register set NXT) -> LDS buffer NXT */ \
         __syncthreads();                                                                                                   \
     }
@@ -401,52 +396,27 @@ static int gemm_launch(const void* A, const void* W, const float* bias, void* C,
     const size_t lds_ab = (size_t)2 * (bm + GBN) * GPITCH * sizeof(bf16_t), lds_c = (size_t)bm * GCP * sizeof(float);
     const size_t lds = lds_ab > lds_c ? lds_ab : lds_c;
     const int total = tiles_m * tiles_n, grid = (total + 7) / 8 * 8;
-#define GM3D_GEMM_LAUNCH_(KTT, WMI, LNA)                                                                                       \
-    {                                                                                                                         \
-        static LdsAttr attr;                                                                                            \
-        if (!attr.ensure((const void*)gemm_tn_bf16_kernel<KTT, WMI, LNA>, lds)) return GM3D_ELAUNCH;                    \
-        hipLaunchKernelGGL((gemm_tn_bf16_kernel<KTT, WMI, LNA>), dim3(grid), dim3(256), lds, (hipStream_t)stream,             \
-                           (const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total,      \
-                           (bf16_t*)G, ldg, (bf16_t*)P, ARG, ldp, bias_after_pool, (const bf16_t*)Fpre, ldfp, colpart,        \
-                           nullptr, ln ? ln->stats : nullptr, ln ? ln->gamma : nullptr, ln ? ln->beta : nullptr,  \
-                           ln ? ln->eps : 0.f, ln ? (bf16_t*)ln->H : nullptr, ln ? ln->mean : nullptr, ln ? ln->rstd : nullptr); \
-    }
-#define GM3D_GEMM_LAUNCH(KTT, WMI) GM3D_GEMM_LAUNCH_(KTT, WMI, false)
-    if (ragged) {
-#define GM3D_GEMM_RAG(WMI)                                                                                                    \
-    {                                                                                                                         \
-        static LdsAttr attr;                                                                                                  \
-        if (!attr.ensure((const void*)gemm_tn_bf16_kernel<0, WMI, false, true>, lds)) return GM3D_ELAUNCH;                    \
-        hipLaunchKernelGGL((gemm_tn_bf16_kernel<0, WMI, false, true>), dim3(grid), dim3(256), lds, (hipStream_t)stream,       \
-                           (const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total,      \
-                           nullptr, 0, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f,  \
-                           nullptr, nullptr, nullptr);                                                                        \
-    }
-        if (bm == 64) GM3D_GEMM_RAG(1) else GM3D_GEMM_RAG(2)
-#undef GM3D_GEMM_RAG
-        GM3D_CHECK_LAUNCH();
-        return GM3D_OK;
-    }
-    if (ln) {       // K = 384: six stages
-        GM3D_GEMM_LAUNCH_(6, 1, true)
-        GM3D_CHECK_LAUNCH();
-        return GM3D_OK;
-    }
-#define GM3D_GEMM_CASE(KTT)                                                                                                   \
-    case KTT:                                                                                                                 \
-        if (bm == 64) GM3D_GEMM_LAUNCH(KTT, 1) else GM3D_GEMM_LAUNCH(KTT, 2)                                                  \
-        break;
+    const GemmLn none{};
+    const GemmLn& l = ln ? *ln : none;
+    // all instances share one argument list (RAG: the plain product, so the epilogue operands are null)
+#define GM3D_GEMM(...)                                                                                                        \
+    launch_lds<gemm_tn_bf16_kernel<__VA_ARGS__>>(dim3(grid), dim3(256), lds, stream, (const bf16_t*)A, (const bf16_t*)W, bias,  \
+                                                 (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total, (bf16_t*)G, ldg, (bf16_t*)P, \
+                                                 ARG, ldp, bias_after_pool, (const bf16_t*)Fpre, ldfp, colpart, (const float*)nullptr, \
+                                                 l.stats, l.gamma, l.beta, l.eps, (bf16_t*)l.H, l.mean, l.rstd)
+    if (ragged) return bm == 64 ? GM3D_GEMM(0, 1, false, true) : GM3D_GEMM(0, 2, false, true);
+    if (ln) return GM3D_GEMM(6, 1, true);       // K = 384: six stages
     switch (K / GBK) {
-        GM3D_GEMM_CASE(2) GM3D_GEMM_CASE(4) GM3D_GEMM_CASE(6) GM3D_GEMM_CASE(8) GM3D_GEMM_CASE(16) GM3D_GEMM_CASE(18)
-        GM3D_GEMM_CASE(24)
-        default:
-            if (bm == 64) GM3D_GEMM_LAUNCH(0, 1) else GM3D_GEMM_LAUNCH(0, 2)
+        case 2: return bm == 64 ? GM3D_GEMM(2, 1, false) : GM3D_GEMM(2, 2, false);
+        case 4: return bm == 64 ? GM3D_GEMM(4, 1, false) : GM3D_GEMM(4, 2, false);
+        case 6: return bm == 64 ? GM3D_GEMM(6, 1, false) : GM3D_GEMM(6, 2, false);
+        case 8: return bm == 64 ? GM3D_GEMM(8, 1, false) : GM3D_GEMM(8, 2, false);
+        case 16: return bm == 64 ? GM3D_GEMM(16, 1, false) : GM3D_GEMM(16, 2, false);
+        case 18: return bm == 64 ? GM3D_GEMM(18, 1, false) : GM3D_GEMM(18, 2, false);
+        case 24: return bm == 64 ? GM3D_GEMM(24, 1, false) : GM3D_GEMM(24, 2, false);
+        default: return bm == 64 ? GM3D_GEMM(0, 1, false) : GM3D_GEMM(0, 2, false);
     }
-#undef GM3D_GEMM_LAUNCH
-#undef GM3D_GEMM_LAUNCH_
-#undef GM3D_GEMM_CASE
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+#undef GM3D_GEMM
 }
 
 extern "C" int gm3d_gemm_tn_bf16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int lda,

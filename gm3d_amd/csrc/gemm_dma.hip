@@ -18,26 +18,11 @@
 // serves the mini-PointNet convolutions over the 262,144 point rows (Encoder.second_conv, P/models_mae_learn_loss.py:878-883, and
 // their input gradients: N = 512 / 256), which are HBM-bound products (A read once + C written once = 400 MB at N = 512): a
 // 128 x 256 tile moves 1 byte from L2 per 85 flops (128 x 128: 64), so the L2 -> CU stream stays below the HBM stream.
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace gm3d {
 
-typedef __bf16 dbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 dbf16x4 __attribute__((ext_vector_type(4)));
-typedef float df32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int DBK = 64;
-
-__device__ __forceinline__ int dma_f(int row) { return (((row >> 1) & 1) << 2) | (((row >> 2) & 1) << 1) | ((row >> 3) & 1); }
-__device__ __forceinline__ int dma_off(int row, int ch) { return row * 128 + ((ch ^ dma_f(row)) << 4); }
-
-__device__ __forceinline__ void dma_glds16(const void* gsrc, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(dst)
-                 : "memory");
-}
 
 // WMI: 32-row MFMA tiles per wave in M (1: 64-row workgroup tile, 2: 128-row)
 // EPI: 0  C = A.W^T (+ bias)
@@ -61,13 +46,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_dma_kernel(const bf16_t* __res
     constexpr int PA = BM / 8, PIECES = (PA + DBN / 8) / 4; // 1-KiB pieces of the A tile; pieces per wave per stage (6 .. 12)
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int per_xcd = gridDim.x >> 3;
-    const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int logical = xcd_tile(blockIdx.x, gridDim.x);
     if (logical >= total_tiles) return;
     const int tile_m = logical / tiles_n, tile_n = logical - tile_m * tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * DBN;
     const int wm = (w >> 1) * 32 * WMI, wn = (w & 1) * 32 * NJ;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)dsm;
+    const unsigned lds0 = lds_addr(dsm);
 
     const int prow = lane >> 3, pslot = lane & 7;
     const bf16_t* src[PIECES];
@@ -77,19 +61,19 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_dma_kernel(const bf16_t* __res
         if (p < PA) {
             const int row = 8 * p + prow;
             const int am = m0 + row < M ? m0 + row : M - 1;          // rows past M: clamped (their outputs are never stored)
-            src[i] = A + (size_t)am * lda + ((pslot ^ dma_f(row)) << 3);
+            src[i] = A + (size_t)am * lda + ((pslot ^ swz(row)) << 3);
         } else {
             const int row = 8 * (p - PA) + prow;
-            src[i] = W + (size_t)(n0 + row) * ldw + ((pslot ^ dma_f(row)) << 3);
+            src[i] = W + (size_t)(n0 + row) * ldw + ((pslot ^ swz(row)) << 3);
         }
     }
 #define GM3D_DMA_STAGE(ST)                                                                          \
     {                                                                                               \
         const unsigned base = lds0 + ((ST) & 1) * STAGE;                                            \
         _Pragma("unroll") for (int i = 0; i < PIECES; ++i)                                          \
-            dma_glds16(src[i] + (size_t)(ST) * DBK, base + 1024 * (w + 4 * i));                     \
+            glds16(src[i] + (size_t)(ST) * DBK, base + 1024 * (w + 4 * i));                         \
     }
-    df32x16 acc[WMI][NJ];
+    f32x16 acc[WMI][NJ];
 #pragma unroll
     for (int i = 0; i < WMI; ++i)
 #pragma unroll
@@ -107,14 +91,14 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_dma_kernel(const bf16_t* __res
         const unsigned char* ws = as + BM * 128;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            dbf16x8 fa[WMI];
+            bf16x8 fa[WMI];
 #pragma unroll
-            for (int i = 0; i < WMI; ++i) fa[i] = *reinterpret_cast<const dbf16x8*>(as + dma_off(wm + 32 * i + r, 2 * s + hh));
+            for (int i = 0; i < WMI; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(as + swz_off(wm + 32 * i + r, 2 * s + hh));
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
-                const dbf16x8 fw = *reinterpret_cast<const dbf16x8*>(ws + dma_off(wn + 32 * j + r, 2 * s + hh));
+                const bf16x8 fw = *reinterpret_cast<const bf16x8*>(ws + swz_off(wn + 32 * j + r, 2 * s + hh));
 #pragma unroll
-                for (int i = 0; i < WMI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw, fa[i], acc[i][j], 0, 0, 0);
+                for (int i = 0; i < WMI; ++i) acc[i][j] = mfma_bf16(fw, fa[i], acc[i][j]);
             }
         }
     }
@@ -136,10 +120,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_dma_kernel(const bf16_t* __res
                     const float4 b = *reinterpret_cast<const float4*>(bias + n0 + col + 8 * q + 4 * hh);
                     v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
                 }
-                dbf16x4 pk;
+                bf16x4 pk;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) pk[e] = (bf16_t)v[e];
-                *reinterpret_cast<dbf16x4*>(img + dma_off(row, cbase + q) + 8 * hh) = pk;
+                *reinterpret_cast<bf16x4*>(img + swz_off(row, cbase + q) + 8 * hh) = pk;
             }
         }
     __syncthreads();
@@ -157,7 +141,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_dma_kernel(const bf16_t* __res
                 for (int e = 0; e < 8; ++e) { best[e] = -INFINITY; bk[e] = 0; }
 #pragma unroll 8
                 for (int k = 0; k < 32; ++k) {
-                    const dbf16x8 f = *reinterpret_cast<const dbf16x8*>(img + dma_off(32 * g + k, chunk & 7));
+                    const bf16x8 f = *reinterpret_cast<const bf16x8*>(img + swz_off(32 * g + k, chunk & 7));
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         const float v = (float)f[e];
@@ -192,12 +176,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_dma_kernel(const bf16_t* __res
         const int c = tid + 256 * i;
         const int t = i / (2 * WMI), row = (c - t * (BM * 8)) >> 3, ch = tid & 7;
         if (m0 + row < M) {
-            const uint4 raw = *reinterpret_cast<const uint4*>(dsm + t * (BM * 128) + dma_off(row, ch));
+            const uint4 raw = *reinterpret_cast<const uint4*>(dsm + t * (BM * 128) + swz_off(row, ch));
             const int n = n0 + 64 * t + 8 * ch;
             if (EPI == 0 || EPI == 3) {
                 *reinterpret_cast<uint4*>(C + (size_t)(m0 + row) * ldc + n) = raw;
             } else {
-                const dbf16x8 f = *reinterpret_cast<const dbf16x8*>(&raw);
+                const bf16x8 f = *reinterpret_cast<const bf16x8*>(&raw);
                 float bv[8], v[8];
                 V8<float>::load(bias + n, bv);
                 if (EPI == 1) {
@@ -255,34 +239,20 @@ static int dma_launch(const void* A, const void* W, const float* bias, void* C, 
     if ((long long)tiles_m * tiles_n > 0x7ffffff0LL) return GM3D_EUNSUPPORTED;
     const int total = tiles_m * tiles_n, grid = (total + 7) / 8 * 8;
     const size_t lds = (size_t)2 * (bm + bn) * 128;
-#define GM3D_DMA_LAUNCH(WMI, EPI, NJ)                                                                                    \
-    {                                                                                                                    \
-        static LdsAttr attr;                                                                                             \
-        if (!attr.ensure((const void*)gemm_tn_dma_kernel<WMI, EPI, NJ>, lds)) return GM3D_ELAUNCH;                       \
-        hipLaunchKernelGGL((gemm_tn_dma_kernel<WMI, EPI, NJ>), dim3(grid), dim3(256), lds, (hipStream_t)stream,          \
-                           (const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total, \
-                           (bf16_t*)G, ldg, (const bf16_t*)Fpre, ldfp, colpart, ARG, bias_after_pool);                   \
-    }
+#define GM3D_DMA(WMI, EPI, NJ)                                                                                            \
+    launch_lds<gemm_tn_dma_kernel<WMI, EPI, NJ>>(dim3(grid), dim3(256), lds, stream, (const bf16_t*)A, (const bf16_t*)W, bias,  \
+                                                 (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total, (bf16_t*)G, ldg,          \
+                                                 (const bf16_t*)Fpre, ldfp, colpart, ARG, bias_after_pool)
     if (ARG) {
-        if (bn == 128) {
-            if (bm == 64) GM3D_DMA_LAUNCH(1, 3, 2) else GM3D_DMA_LAUNCH(2, 3, 2)
-        } else {
-            if (bm == 64) GM3D_DMA_LAUNCH(1, 3, 3) else GM3D_DMA_LAUNCH(2, 3, 3)
-        }
-    } else if (Fpre) {
-        if (bm == 64) GM3D_DMA_LAUNCH(1, 2, 3) else GM3D_DMA_LAUNCH(2, 2, 3)
-    } else if (G) {
-        if (bm == 64) GM3D_DMA_LAUNCH(1, 1, 3) else GM3D_DMA_LAUNCH(2, 1, 3)
-    } else if (bn == 192) {
-        if (bm == 64) GM3D_DMA_LAUNCH(1, 0, 3) else GM3D_DMA_LAUNCH(2, 0, 3)
-    } else if (bn == 128) {
-        if (bm == 64) GM3D_DMA_LAUNCH(1, 0, 2) else GM3D_DMA_LAUNCH(2, 0, 2)
-    } else {
-        if (bm == 64) GM3D_DMA_LAUNCH(1, 0, 4) else GM3D_DMA_LAUNCH(2, 0, 4)
+        if (bn == 128) return bm == 64 ? GM3D_DMA(1, 3, 2) : GM3D_DMA(2, 3, 2);
+        return bm == 64 ? GM3D_DMA(1, 3, 3) : GM3D_DMA(2, 3, 3);
     }
-#undef GM3D_DMA_LAUNCH
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    if (Fpre) return bm == 64 ? GM3D_DMA(1, 2, 3) : GM3D_DMA(2, 2, 3);
+    if (G) return bm == 64 ? GM3D_DMA(1, 1, 3) : GM3D_DMA(2, 1, 3);
+    if (bn == 192) return bm == 64 ? GM3D_DMA(1, 0, 3) : GM3D_DMA(2, 0, 3);
+    if (bn == 128) return bm == 64 ? GM3D_DMA(1, 0, 2) : GM3D_DMA(2, 0, 2);
+    return bm == 64 ? GM3D_DMA(1, 0, 4) : GM3D_DMA(2, 0, 4);
+#undef GM3D_DMA
 }
 
 extern "C" int gm3d_gemm_tn_bf16_dma(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int lda, int ldw,

@@ -16,14 +16,9 @@
 // 48 KiB of LDS -> three workgroups per CU, or two beside a workgroup of the backward chain the launch runs next to.  Long reductions over few output tiles (the 4-block decoders: 27 tiles per
 // weight kind and block) are split over row ranges into fp32 partial slabs that gm3d_sum_few_rows adds in a fixed order
 // (deterministic; no atomics).
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace gm3d {
-
-typedef __bf16 nbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 nbf16x4 __attribute__((ext_vector_type(4)));
-typedef float nf32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) nbf16x4 lds_nbf16x4;
 
 constexpr int NT_BR = 32;                 // reduction rows per stage
 constexpr int NT_TILE = NT_BR * 256;      // bytes of one [32][128] bf16 tile
@@ -32,25 +27,15 @@ constexpr int NT_NBUF = 3;
 
 __device__ __forceinline__ int nt_f(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
-// one LDS-DMA piece: 64 lanes x 16 bytes -> 1 KiB at the wave-uniform LDS byte address `dst`; the compiler does not see this
-// load (no automatic s_waitcnt vmcnt(0) before the next LDS read): completion is counted by hand below
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(dst)
-                 : "memory");
-}
-
 // fragment for mfma_32x32x16 out of a [32 rows][128 cols] image: element j of this lane = M[k = kk0 + 8 hh + j][col], the lane's
 // column being colblk + (lane & 15), colblk a multiple of 16 that already includes this lane's 16-lane group
-__device__ __forceinline__ nbf16x8 nt_frag(const unsigned char* img, int kk0, int hh, int colblk, int lane) {
+__device__ __forceinline__ bf16x8 nt_frag(const unsigned char* img, int kk0, int hh, int colblk, int lane) {
     const int l16 = lane & 15, q = l16 >> 2, p = l16 & 3;
     const int col = colblk + 4 * p, ch = col >> 3, sub = (col >> 2) & 1;
     const int r0 = kk0 + 8 * hh + q, r1 = r0 + 4;
-    const nbf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_nbf16x4*)(img + 256 * r0 + 16 * (ch ^ nt_f(r0)) + 8 * sub));
-    const nbf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_nbf16x4*)(img + 256 * r1 + 16 * (ch ^ nt_f(r1)) + 8 * sub));
-    nbf16x8 v;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(img + 256 * r0 + 16 * (ch ^ nt_f(r0)) + 8 * sub));
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(img + 256 * r1 + 16 * (ch ^ nt_f(r1)) + 8 * sub));
+    bf16x8 v;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { v[j] = lo[j]; v[4 + j] = hi[j]; }
     return v;
@@ -79,7 +64,7 @@ __device__ __forceinline__ void nt_tile(unsigned char* nsm, const bf16_t* __rest
 
     // staging role of this lane: each wave moves pieces w and w + 4 of both tiles (a piece = 4 rows x 256 B = 1 KiB)
     const int prow = lane >> 4, pcs = lane & 15;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)nsm;
+    const unsigned lds0 = lds_addr(nsm);
     size_t yoff[2], xoff[2];
     // ragged N / K (multiples of 8: the 96 / 192 / 288 / 576-wide layers of Point-M2AE): chunks past the matrix edge are redirected to
     // the tile's last valid chunk (in bounds; they only feed output elements that are never stored)
@@ -101,7 +86,7 @@ __device__ __forceinline__ void nt_tile(unsigned char* nsm, const bf16_t* __rest
         }                                                                                                    \
     }
 
-    nf32x16 acc[2][2];
+    f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -127,7 +112,7 @@ __device__ __forceinline__ void nt_tile(unsigned char* nsm, const bf16_t* __rest
         const unsigned char* xs = ys + NT_TILE;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            nbf16x8 fa[2], fb[2];
+            bf16x8 fa[2], fb[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) fa[i] = nt_frag(ys, 16 * ks, hh, wn + 32 * i + cb, lane);      // A[i = n][k = row]
 #pragma unroll
@@ -135,7 +120,7 @@ __device__ __forceinline__ void nt_tile(unsigned char* nsm, const bf16_t* __rest
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 2; ++j) acc[i][j] = mfma_bf16(fa[i], fb[j], acc[i][j]);
         }
     }
 #undef GM3D_NT_STAGE
@@ -190,8 +175,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_kernel(const bf16_t* __re
                                                               int* __restrict__ counters, float* __restrict__ Ofin, long long sOfin,
                                                               int ldofin) {
     extern __shared__ __attribute__((aligned(16))) unsigned char nsm[];
-    const int per_xcd = gridDim.x >> 3;
-    const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int logical = xcd_tile(blockIdx.x, gridDim.x);
     if (logical >= total) return;
     nt_tile(nsm, Y, X, O, rows_split, ldy, ldx, ldo, sY, sX, sO, sOs, splits, tiles_n, tiles_k, logical, Nfull, Kfull, counters, Ofin, sOfin,
             ldofin);
@@ -251,8 +235,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt384_bf16_kernel(const bf16_t* _
     extern __shared__ __attribute__((aligned(16))) unsigned char nsm[];
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int per_xcd = gridDim.x >> 3;
-    const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int logical = xcd_tile(blockIdx.x, gridDim.x);
     if (logical >= total) return;
     int t = logical;
     const int tk = t % tiles_k; t /= tiles_k;
@@ -266,7 +249,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt384_bf16_kernel(const bf16_t* _
     const int nst = rows_split / NT_BR;
 
     const int prow = lane >> 4, pcs = lane & 15;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)nsm;
+    const unsigned lds0 = lds_addr(nsm);
     const int srow = 4 * w + prow;                              // the row of every image this lane stages
     const int sch = pcs ^ nt_f(srow);                           // ... and the source chunk that belongs at its LDS slot
     const size_t yoff = (size_t)srow * ldy + sch * 8, xoff = (size_t)srow * ldx + sch * 8;
@@ -278,7 +261,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt384_bf16_kernel(const bf16_t* _
         _Pragma("unroll") for (int i = 0; i < 3; ++i) glds16(Xb + ro * ldx + xoff + 128 * i, base + (1 + i) * NB_IMG); \
     }
 
-    nf32x16 acc[2][3];
+    f32x16 acc[2][3];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -308,19 +291,19 @@ __global__ __launch_bounds__(512, 1) void gemm_nt384_bf16_kernel(const bf16_t* _
             fad[2 * f + 1] = lds0 + img * NB_IMG + 256 * r1 + 16 * (ch ^ nt_f(r1)) + 8 * sub;
         }
     }
-    nbf16x8 fa0[2], fb0[3], fa1[2], fb1[3];
+    bf16x8 fa0[2], fb0[3], fa1[2], fb1[3];
 #define GM3D_NB_FRAGS(FA, FB, OFF)                                                                           \
     _Pragma("unroll") for (int f = 0; f < 5; ++f) {                                                          \
-        const nbf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_nbf16x4*)(fad[2 * f] + (OFF)));     \
-        const nbf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_nbf16x4*)(fad[2 * f + 1] + (OFF))); \
-        nbf16x8 v;                                                                                           \
+        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(fad[2 * f] + (OFF)));       \
+        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(fad[2 * f + 1] + (OFF)));   \
+        bf16x8 v;                                                                                            \
         _Pragma("unroll") for (int e = 0; e < 4; ++e) { v[e] = lo[e]; v[4 + e] = hi[e]; }                    \
         if (f < 2) FA[f] = v; else FB[f - 2] = v;                                                            \
     }
 #define GM3D_NB_MFMA(FA, FB, I0, I1)                                                                         \
     _Pragma("unroll") for (int i = I0; i < I1; ++i)                                                          \
         _Pragma("unroll") for (int j = 0; j < 3; ++j)                                                        \
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FA[i], FB[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = mfma_bf16(FA[i], FB[j], acc[i][j]);
 
     GM3D_NB_STAGE(0)
     if (nst > 1) GM3D_NB_STAGE(1)
@@ -423,25 +406,18 @@ static int nt_launch(const void* dY, const void* X, float* out, int batch, int R
         if (total > 0x7ffffff0LL) return GM3D_EUNSUPPORTED;
         const int grid = (int)((total + 7) / 8 * 8);
         const size_t lds = (size_t)NB_NBUF * NB_STAGE;
-        static LdsAttr attr;
-        if (!attr.ensure((const void*)gemm_nt384_bf16_kernel, lds)) return GM3D_ELAUNCH;
-        hipLaunchKernelGGL(gemm_nt384_bf16_kernel, dim3(grid), dim3(512), lds, (hipStream_t)stream, (const bf16_t*)dY, (const bf16_t*)X, out,
-                           R / splits, ldy, ldx, ldo, stride_y, stride_x, stride_o, stride_split, splits, N / 128, K / 384, (int)total);
-        GM3D_CHECK_LAUNCH();
-        return GM3D_OK;
+        return launch_lds<gemm_nt384_bf16_kernel>(dim3(grid), dim3(512), lds, stream, (const bf16_t*)dY, (const bf16_t*)X, out, R / splits,
+                                                  ldy, ldx, ldo, stride_y, stride_x, stride_o, stride_split, splits, N / 128, K / 384,
+                                                  (int)total);
     }
     const int tn_ = (N + 127) / 128, tk_ = (K + 127) / 128;
     const long long total = (long long)batch * splits * tn_ * tk_;
     if (total > 0x7ffffff0LL) return GM3D_EUNSUPPORTED;
     const int grid = (int)((total + 7) / 8 * 8);
     const size_t lds = (size_t)NT_NBUF * NT_STAGE;
-    static LdsAttr attr;
-    if (!attr.ensure((const void*)gemm_nt_bf16_kernel, lds)) return GM3D_ELAUNCH;
-    hipLaunchKernelGGL(gemm_nt_bf16_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)dY, (const bf16_t*)X, out,
-                       R / splits, ldy, ldx, ldo, stride_y, stride_x, stride_o, stride_split, splits, tn_, tk_, (int)total, N, K, counters, fin,
-                       stride_fin, ldfin);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<gemm_nt_bf16_kernel>(dim3(grid), dim3(256), lds, stream, (const bf16_t*)dY, (const bf16_t*)X, out, R / splits, ldy,
+                                           ldx, ldo, stride_y, stride_x, stride_o, stride_split, splits, tn_, tk_, (int)total, N, K, counters,
+                                           fin, stride_fin, ldfin);
 }
 
 extern "C" int gm3d_gemm_nt_bf16(const void* dY, const void* X, float* out, int batch, int R, int N, int K, int ldy, int ldx, int ldo,
@@ -554,10 +530,8 @@ extern "C" int gm3d_gemm_nt_bf16_multi(int count, const void* const* dY, const v
     for (int j = count; j < NT_MAXP; ++j) m.p[j] = m.p[0];
     for (int j = sm.count; j < NT_MAXP; ++j) sm.j[j] = sm.j[0];
     const size_t lds = (size_t)NT_NBUF * NT_STAGE;
-    static LdsAttr attr;
-    if (!attr.ensure((const void*)gemm_nt_multi_kernel, lds)) return GM3D_ELAUNCH;
-    hipLaunchKernelGGL(gemm_nt_multi_kernel, dim3((unsigned)first), dim3(256), lds, (hipStream_t)stream, m);
-    GM3D_CHECK_LAUNCH();
+    const int rc = launch_lds<gemm_nt_multi_kernel>(dim3((unsigned)first), dim3(256), lds, stream, m);
+    if (rc != GM3D_OK) return rc;
     if (sm.count > 0) {
         if (max_batch > 65535) return GM3D_EUNSUPPORTED;
         const int gx = (int)((max_cols4 + 255) / 256 < 256 ? (max_cols4 + 255) / 256 : 256);

@@ -9,27 +9,13 @@
 // (two stages = 48 KB) gets about half the ~70 GB/s a CU can pull from L2 (DESIGN 3b'): the tuned library wins 0.65x there.
 // This kernel keeps FOUR stages in an LDS ring filled by LDS-DMA (global_load_lds_dwordx4, no staging registers), two of them in
 // flight behind a counted s_waitcnt vmcnt, one raw s_barrier per stage.  The LDS image is the conflict-free 128-byte-row image of
-// csrc/attention.hip (16-byte chunk ch of row r at 128 r + 16 (ch ^ f(r))); LDS-DMA writes lane-linear, so the XOR is applied
+// mfma.hpp (16-byte chunk ch of row r at swz_off(r, ch) = 128 r + 16 (ch ^ swz(r))); LDS-DMA writes lane-linear, so the XOR is applied
 // to the per-lane SOURCE address.  MFMA loop and epilogue as in gemm.hip (transposed product: lanes = rows of C).
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace gm3d {
 
-typedef __bf16 rbf16x8 __attribute__((ext_vector_type(8)));
-typedef float rf32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int RBN = 128, RBK = 64, RNBUF = 4, RCP = 132;
-
-__device__ __forceinline__ int ring_f(int row) { return (((row >> 1) & 1) << 2) | (((row >> 2) & 1) << 1) | ((row >> 3) & 1); }
-__device__ __forceinline__ int ring_off(int row, int ch) { return row * 128 + ((ch ^ ring_f(row)) << 4); }
-
-__device__ __forceinline__ void ring_glds16(const void* gsrc, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(dst)
-                 : "memory");
-}
 
 // WMI: 32-row MFMA tiles per wave in M (1: 64-row workgroup tile, 2: 128-row)
 // RES: residual epilogue of a transformer block's proj / fc2 (N = 384 = the LayerNorm width): instead of C the kernel writes the
@@ -53,13 +39,12 @@ __global__ __launch_bounds__(256) void gemm_tn_ring_kernel(const bf16_t* __restr
     constexpr int PA = BM / 8, PIECES = (PA + 16) / 4;      // 1-KiB pieces of the A tile; pieces per wave per stage (6 or 8)
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int per_xcd = gridDim.x >> 3;
-    const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int logical = xcd_tile(blockIdx.x, gridDim.x);
     if (logical >= total_tiles) return;
     const int tile_m = logical / tiles_n, tile_n = logical - tile_m * tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * RBN;
     const int wm = (w >> 1) * 32 * WMI, wn = (w & 1) * 64;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)rsm;
+    const unsigned lds0 = lds_addr(rsm);
 
     // this lane's share of a stage: pieces p = w + 4 i (i < PIECES); piece p < PA: A rows 8p .. 8p+7, else W rows 8(p-PA) ..
     const int prow = lane >> 3, pslot = lane & 7;
@@ -70,11 +55,11 @@ __global__ __launch_bounds__(256) void gemm_tn_ring_kernel(const bf16_t* __restr
         if (p < PA) {
             const int row = 8 * p + prow;
             const int am = m0 + row < M ? m0 + row : M - 1;          // rows past M: clamped (their outputs are never stored)
-            src[i] = A + (size_t)am * lda + ((pslot ^ ring_f(row)) << 3);
+            src[i] = A + (size_t)am * lda + ((pslot ^ swz(row)) << 3);
         } else {
             const int row = 8 * (p - PA) + prow;
             const int wn_ = n0 + row < N ? n0 + row : N - 1;          // columns past N (a ragged last tile): clamped, never stored
-            src[i] = W + (size_t)wn_ * ldw + ((pslot ^ ring_f(row)) << 3);
+            src[i] = W + (size_t)wn_ * ldw + ((pslot ^ swz(row)) << 3);
         }
     }
     constexpr int NBUF = DEPTH + 2;
@@ -82,10 +67,10 @@ __global__ __launch_bounds__(256) void gemm_tn_ring_kernel(const bf16_t* __restr
     {                                                                                                \
         const unsigned base = lds0 + ((ST) % NBUF) * STAGE;                                          \
         _Pragma("unroll") for (int i = 0; i < PIECES; ++i)                                           \
-            ring_glds16(src[i] + (size_t)(ST) * RBK, base + 1024 * (w + 4 * i));                     \
+            glds16(src[i] + (size_t)(ST) * RBK, base + 1024 * (w + 4 * i));                          \
     }
 
-    rf32x16 acc[WMI][2];
+    f32x16 acc[WMI][2];
 #pragma unroll
     for (int i = 0; i < WMI; ++i)
 #pragma unroll
@@ -112,20 +97,20 @@ __global__ __launch_bounds__(256) void gemm_tn_ring_kernel(const bf16_t* __restr
         __builtin_amdgcn_s_barrier();
         const unsigned char* as = rsm + (kt % NBUF) * STAGE;
         const unsigned char* ws = as + BM * 128;
-        rbf16x8 fa[4][WMI], fw[4][2];
+        bf16x8 fa[4][WMI], fw[4][2];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
 #pragma unroll
-            for (int i = 0; i < WMI; ++i) fa[s][i] = *reinterpret_cast<const rbf16x8*>(as + ring_off(wm + 32 * i + r, 2 * s + hh));
+            for (int i = 0; i < WMI; ++i) fa[s][i] = *reinterpret_cast<const bf16x8*>(as + swz_off(wm + 32 * i + r, 2 * s + hh));
 #pragma unroll
-            for (int j = 0; j < 2; ++j) fw[s][j] = *reinterpret_cast<const rbf16x8*>(ws + ring_off(wn + 32 * j + r, 2 * s + hh));
+            for (int j = 0; j < 2; ++j) fw[s][j] = *reinterpret_cast<const bf16x8*>(ws + swz_off(wn + 32 * j + r, 2 * s + hh));
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
             for (int i = 0; i < WMI; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[s][j], fa[s][i], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < 2; ++j) acc[i][j] = mfma_bf16(fw[s][j], fa[s][i], acc[i][j]);
     }
 #undef GM3D_RING_STAGE
     __syncthreads();                 // every wave is done with the ring: it becomes the fp32 staging tile of the epilogue
@@ -207,7 +192,6 @@ __global__ __launch_bounds__(256) void gemm_tn_ring_kernel(const bf16_t* __restr
     }
 }
 
-
 // ---- 96-column form: N = 384 as FOUR column tiles ----------------------------------------------------------------------------
 // With 128-column tiles an N = 384 product has 3 tiles per row block: 150 (3200 rows) / 192 (4096, or 8192 in 128-row tiles)
 // workgroups for 256 CUs, and what bounds each of them is the bytes its CU pulls from L2 (DESIGN 3b').  Four 96-column tiles per
@@ -228,12 +212,11 @@ __global__ __launch_bounds__(192) void gemm_tn_ring96_kernel(const bf16_t* __res
     constexpr int PMAX = (NP + 2) / 3;                      // pieces of wave 0 (7 / 10); waves 1, 2 may have one fewer
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int per_xcd = gridDim.x >> 3;
-    const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int logical = xcd_tile(blockIdx.x, gridDim.x);
     if (logical >= total_tiles) return;
     const int tile_m = logical / tiles_n, tile_n = logical - tile_m * tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * R96;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)rsm;
+    const unsigned lds0 = lds_addr(rsm);
     const int mine = (NP - w + 2) / 3;                      // pieces p = w + 3 i < NP
 
     const int prow = lane >> 3, pslot = lane & 7;
@@ -244,19 +227,19 @@ __global__ __launch_bounds__(192) void gemm_tn_ring96_kernel(const bf16_t* __res
         if (p < PA) {
             const int row = 8 * p + prow;
             const int am = m0 + row < M ? m0 + row : M - 1;
-            src[i] = A + (size_t)am * lda + ((pslot ^ ring_f(row)) << 3);
+            src[i] = A + (size_t)am * lda + ((pslot ^ swz(row)) << 3);
         } else {
             const int row = 8 * (p - PA) + prow;
-            src[i] = W + (size_t)(n0 + row) * ldw + ((pslot ^ ring_f(row)) << 3);
+            src[i] = W + (size_t)(n0 + row) * ldw + ((pslot ^ swz(row)) << 3);
         }
     }
 #define GM3D_R96_STAGE(ST)                                                                           \
     {                                                                                                \
         const unsigned base = lds0 + ((ST) % RNBUF) * STAGE;                                         \
         _Pragma("unroll") for (int i = 0; i < PMAX; ++i)                                             \
-            if (i < mine) ring_glds16(src[i] + (size_t)(ST) * RBK, base + 1024 * (w + 3 * i));       \
+            if (i < mine) glds16(src[i] + (size_t)(ST) * RBK, base + 1024 * (w + 3 * i));            \
     }
-    rf32x16 acc[NMT];
+    f32x16 acc[NMT];
 #pragma unroll
     for (int i = 0; i < NMT; ++i)
 #pragma unroll
@@ -280,17 +263,17 @@ __global__ __launch_bounds__(192) void gemm_tn_ring96_kernel(const bf16_t* __res
         __builtin_amdgcn_s_barrier();
         const unsigned char* as = rsm + (kt % RNBUF) * STAGE;
         const unsigned char* ws = as + BM * 128;
-        rbf16x8 fa[4][NMT], fw[4];
+        bf16x8 fa[4][NMT], fw[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
 #pragma unroll
-            for (int i = 0; i < NMT; ++i) fa[s][i] = *reinterpret_cast<const rbf16x8*>(as + ring_off(32 * i + r, 2 * s + hh));
-            fw[s] = *reinterpret_cast<const rbf16x8*>(ws + ring_off(32 * w + r, 2 * s + hh));
+            for (int i = 0; i < NMT; ++i) fa[s][i] = *reinterpret_cast<const bf16x8*>(as + swz_off(32 * i + r, 2 * s + hh));
+            fw[s] = *reinterpret_cast<const bf16x8*>(ws + swz_off(32 * w + r, 2 * s + hh));
         }
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
-            for (int i = 0; i < NMT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[s], fa[s][i], acc[i], 0, 0, 0);
+            for (int i = 0; i < NMT; ++i) acc[i] = mfma_bf16(fw[s], fa[s][i], acc[i]);
     }
 #undef GM3D_R96_STAGE
     __syncthreads();
@@ -349,24 +332,14 @@ static int ring_launch(const void* A, const void* W, const float* bias, void* C,
     const int total = tiles_m * tiles_n, grid = (total + 7) / 8 * 8;
     const int depth = U ? 2 : RING_DEPTH[bm == 64 ? 0 : 1];
     const size_t lds = (size_t)(depth + 2) * (bm + RBN) * 128;
-#define GM3D_RING_LAUNCH(WMI, RES, DEPTH)                                                                                 \
-    {                                                                                                                    \
-        static LdsAttr attr;                                                                                             \
-        if (!attr.ensure((const void*)gemm_tn_ring_kernel<WMI, RES, DEPTH>, lds)) return GM3D_ELAUNCH;                   \
-        hipLaunchKernelGGL((gemm_tn_ring_kernel<WMI, RES, DEPTH>), dim3(grid), dim3(256), lds, (hipStream_t)stream,      \
-                           (const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total, \
-                           res, rowscale, rows_per_sample, (const bf16_t*)add, U, stats, (bf16_t*)U16);                  \
-    }
-    if (U) {
-        if (bm == 64) GM3D_RING_LAUNCH(1, true, 2) else GM3D_RING_LAUNCH(2, true, 2)
-    } else if (bm == 64) {
-        if (depth == 2) GM3D_RING_LAUNCH(1, false, 2) else if (depth == 3) GM3D_RING_LAUNCH(1, false, 3) else GM3D_RING_LAUNCH(1, false, 4)
-    } else {
-        if (depth == 2) GM3D_RING_LAUNCH(2, false, 2) else GM3D_RING_LAUNCH(2, false, 3)
-    }
-#undef GM3D_RING_LAUNCH
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+#define GM3D_RING(WMI, RES, DEPTH)                                                                                         \
+    launch_lds<gemm_tn_ring_kernel<WMI, RES, DEPTH>>(dim3(grid), dim3(256), lds, stream, (const bf16_t*)A, (const bf16_t*)W, bias, \
+                                                     (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total, res, rowscale,           \
+                                                     rows_per_sample, (const bf16_t*)add, U, stats, (bf16_t*)U16)
+    if (U) return bm == 64 ? GM3D_RING(1, true, 2) : GM3D_RING(2, true, 2);
+    if (bm == 64) return depth == 2 ? GM3D_RING(1, false, 2) : depth == 3 ? GM3D_RING(1, false, 3) : GM3D_RING(1, false, 4);
+    return depth == 2 ? GM3D_RING(2, false, 2) : GM3D_RING(2, false, 3);
+#undef GM3D_RING
 }
 
 extern "C" int gm3d_gemm_tn_bf16_ring(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int lda, int ldw,
@@ -386,19 +359,11 @@ extern "C" int gm3d_gemm_tn_bf16_ring96(const void* A, const void* W, const floa
     if ((long long)tiles_m * tiles_n > 0x7ffffff0LL) return GM3D_EUNSUPPORTED;
     const int total = tiles_m * tiles_n, grid = (total + 7) / 8 * 8;
     const size_t lds = (size_t)RNBUF * (bm + R96) * 128;
-    if (bm == 64) {
-        static LdsAttr attr;
-        if (!attr.ensure((const void*)gemm_tn_ring96_kernel<1>, lds)) return GM3D_ELAUNCH;
-        hipLaunchKernelGGL((gemm_tn_ring96_kernel<1>), dim3(grid), dim3(192), lds, (hipStream_t)stream, (const bf16_t*)A, (const bf16_t*)W,
-                           bias, (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total);
-    } else {
-        static LdsAttr attr;
-        if (!attr.ensure((const void*)gemm_tn_ring96_kernel<2>, lds)) return GM3D_ELAUNCH;
-        hipLaunchKernelGGL((gemm_tn_ring96_kernel<2>), dim3(grid), dim3(192), lds, (hipStream_t)stream, (const bf16_t*)A, (const bf16_t*)W,
-                           bias, (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total);
-    }
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    if (bm == 64)
+        return launch_lds<gemm_tn_ring96_kernel<1>>(dim3(grid), dim3(192), lds, stream, (const bf16_t*)A, (const bf16_t*)W, bias,
+                                                    (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total);
+    return launch_lds<gemm_tn_ring96_kernel<2>>(dim3(grid), dim3(192), lds, stream, (const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C,
+                                                M, N, K, lda, ldw, ldc, tiles_n, total);
 }
 
 extern "C" int gm3d_gemm_tn_bf16_res(const void* A, const void* W, const float* bias, const float* res, const float* rowscale,

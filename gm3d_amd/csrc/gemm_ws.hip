@@ -16,24 +16,9 @@
 // tile with its resident W fragments (K/16 MFMA 32x32x16, k ascending: the accumulation order of csrc/gemm.hip -> identical
 // bits), the 32 x BN result is staged in LDS as bf16 and leaves as whole rows; the max-pool epilogue reduces the staged tile --
 // exactly one group -- down its 32 rows.  L2 -> CU traffic: A once per column block of 32 NW columns, nothing else.
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace gm3d {
-
-typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wbf16x4 __attribute__((ext_vector_type(4)));
-typedef float wf32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int ws_f(int row) { return (((row >> 1) & 1) << 2) | (((row >> 2) & 1) << 1) | ((row >> 3) & 1); }
-__device__ __forceinline__ int ws_off(int row, int ch) { return row * 128 + ((ch ^ ws_f(row)) << 4); }
-
-__device__ __forceinline__ void ws_glds16(const void* gsrc, unsigned dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(dst)
-                 : "memory");
-}
 
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n <= 48 (the immediate must be a constant: one uniform branch)
 __device__ __forceinline__ void ws_wait_vm(int n) {
@@ -94,13 +79,12 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
     unsigned char* stage = wsm + NT * TILE;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const int per_xcd = gridDim.x >> 3;
-    const int logical = (blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);      // column blocks of one row stream share an XCD's L2
+    const int logical = xcd_tile(blockIdx.x, gridDim.x);      // column blocks of one row stream share an XCD's L2
     const int tile_n = logical % tiles_n, first = logical / tiles_n, stride = gridDim.x / tiles_n;
     const int tiles_m = (M + 32 * TM - 1) / (32 * TM);
     const int nmine = first < tiles_m ? (tiles_m - first + stride - 1) / stride : 0;
     const int n0 = tile_n * BN;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)wsm;
+    const unsigned lds0 = lds_addr(wsm);
 
     if (w >= NW) {
         // ------------------------------------------------------------------ loader wave(s): nothing but LDS-DMA and barriers
@@ -113,9 +97,9 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
                 const int p = lw * PPL + q, t = p / (4 * KT), pp = p - t * (4 * KT), kt = pp >> 2, row = 8 * (pp & 3) + prow;
                 const int gr = m0 + 32 * t + row;
                 const int am = gr < M ? gr : M - 1;                  // rows past M: clamped (their outputs are never stored)
-                int col = 64 * kt + ((pslot ^ ws_f(row)) << 3);
+                int col = 64 * kt + ((pslot ^ swz(row)) << 3);
                 col = col < Kreal ? col : 0;
-                ws_glds16(A + (size_t)am * lda + col, base + 1024 * p);
+                glds16(A + (size_t)am * lda + col, base + 1024 * p);
             }
         };
         for (int d = 0; d < DEPTH && d < nmine; ++d) issue(d);
@@ -132,14 +116,14 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
     }
 
     // ---------------------------------------------------------------------- compute waves: W fragments resident in registers
-    wbf16x8 wreg[KT][4];
+    bf16x8 wreg[KT][4];
     {
         const bf16_t* wp = W + (size_t)(n0 + 32 * w + r) * ldw + 8 * hh;
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                if (64 * kt + 16 * s + 8 * hh < Kreal) wreg[kt][s] = *reinterpret_cast<const wbf16x8*>(wp + 64 * kt + 16 * s);
+                if (64 * kt + 16 * s + 8 * hh < Kreal) wreg[kt][s] = *reinterpret_cast<const bf16x8*>(wp + 64 * kt + 16 * s);
                 else
 #pragma unroll
                     for (int e = 0; e < 8; ++e) wreg[kt][s][e] = (bf16_t)0.0f;
@@ -204,18 +188,18 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
         }
         __builtin_amdgcn_s_barrier();                // B1
         const unsigned char* as = wsm + (i % NT) * TILE;
-        wf32x16 acc[TM];
+        f32x16 acc[TM];
 #pragma unroll
         for (int t = 0; t < TM; ++t)
 #pragma unroll
             for (int g = 0; g < 16; ++g) acc[t][g] = 0.f;
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) {
-            wbf16x8 fa[TM][4];
+            bf16x8 fa[TM][4];
 #pragma unroll
             for (int t = 0; t < TM; ++t)
 #pragma unroll
-                for (int s = 0; s < 4; ++s) fa[t][s] = *reinterpret_cast<const wbf16x8*>(as + t * HALF + kt * 4096 + ws_off(r, 2 * s + hh));
+                for (int s = 0; s < 4; ++s) fa[t][s] = *reinterpret_cast<const bf16x8*>(as + t * HALF + kt * 4096 + swz_off(r, 2 * s + hh));
             // EPI 0: the transposed tile (lane = row, registers = 4 x 4 consecutive columns: whole-row staging).  EPI 3: operands
             // swapped -> lane = COLUMN (lane & 31), registers = 16 of the 32 rows (8 (g >> 2) + 4 hh + (g & 3)), the other 16 in lane ^ 32:
             // the max over rows is 15 register maxima + one cross-lane step.  Same products, same k order: same bits.
@@ -223,8 +207,8 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
             for (int s = 0; s < 4; ++s)
 #pragma unroll
                 for (int t = 0; t < TM; ++t)
-                    acc[t] = EPI == 3 ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[t][s], wreg[kt][s], acc[t], 0, 0, 0)
-                                      : __builtin_amdgcn_mfma_f32_32x32x16_bf16(wreg[kt][s], fa[t][s], acc[t], 0, 0, 0);
+                    acc[t] = EPI == 3 ? mfma_bf16(fa[t][s], wreg[kt][s], acc[t])
+                                      : mfma_bf16(wreg[kt][s], fa[t][s], acc[t]);
         }
         if (EPI == 3 && !C) __builtin_amdgcn_s_barrier();      // B2 (no rows to stage): tile i's slot may be refilled from here on
         if (EPI == 3) {
@@ -286,7 +270,7 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
 #pragma unroll
                 for (int g = 0; g < 16; ++g) {
                     const int row = 8 * (g >> 2) + 4 * hh + (g & 3);
-                    *reinterpret_cast<unsigned short*>(img + ws_off(row, ch) + sub) = rowbits[t][g];
+                    *reinterpret_cast<unsigned short*>(img + swz_off(row, ch) + sub) = rowbits[t][g];
                 }
             }
         } else {
@@ -297,7 +281,7 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
                 unsigned char* img = stage + (t * NIMG + ((32 * w) >> 6)) * 4096;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    wbf16x4 pk;
+                    bf16x4 pk;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         pk[e] = (bf16_t)(acc[t][4 * q + e] + bq[q][e]);
@@ -311,7 +295,7 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
                             bn_b[q][e] += y * y;
                         }
                     }
-                    *reinterpret_cast<wbf16x4*>(img + ws_off(r, cbase + q) + 8 * hh) = pk;
+                    *reinterpret_cast<bf16x4*>(img + swz_off(r, cbase + q) + 8 * hh) = pk;
                 }
             }
         }
@@ -328,7 +312,7 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
                 if (c < 32 * TM * CH) {
                     const int row = c / CH, chunk = c - row * CH;
                     if (m0 + row < M) {
-                        const uint4 raw = *reinterpret_cast<const uint4*>(stage + ((row >> 5) * NIMG + (chunk >> 3)) * 4096 + ws_off(row & 31, chunk & 7));
+                        const uint4 raw = *reinterpret_cast<const uint4*>(stage + ((row >> 5) * NIMG + (chunk >> 3)) * 4096 + swz_off(row & 31, chunk & 7));
                         *reinterpret_cast<uint4*>(C + (size_t)(m0 + row) * ldc + n0 + 8 * chunk) = raw;
                     }
                 }
@@ -385,7 +369,6 @@ static int ws_launch(const void* A, const void* W, const float* bias, void* C, v
     if (K % 8 || K > 512 || lda % 8 || ldw % 8 || lda < K || ldw < K || (C && (ldc % 8 || ldc < N))) return GM3D_EUNSUPPORTED;
     if (((size_t)A | (size_t)W | (size_t)C) & 15) return GM3D_EUNSUPPORTED;
     if (M == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
 #define GM3D_WS_LAUNCH(KT, NW, NL, EPI, TM)                                                                               \
     {                                                                                                                    \
         constexpr int TILE_ = TM * KT * 4096, STAGE_ = TM * ((32 * NW + 63) / 64) * 4096;                                \
@@ -393,13 +376,9 @@ static int ws_launch(const void* A, const void* W, const float* bias, void* C, v
         const size_t lds = (size_t)(DEPTH_ + 1) * TILE_ + STAGE_;                                                        \
         const int tiles_m = (M + 32 * TM - 1) / (32 * TM);                                                               \
         const int tiles_n = N / (32 * NW), grid = ws_grid(tiles_m, tiles_n, lds);                                        \
-        static LdsAttr attr;                                                                                             \
-        if (!attr.ensure((const void*)gemm_tn_ws_kernel<KT, NW, NL, EPI, TM>, lds)) return GM3D_ELAUNCH;                 \
-        hipLaunchKernelGGL((gemm_tn_ws_kernel<KT, NW, NL, EPI, TM>), dim3(grid), dim3(64 * (NW + NL)), lds, st,          \
-                           (const bf16_t*)A, (const bf16_t*)W, bias, (bf16_t*)C, M, N, lda, ldw, ldc, tiles_n, (bf16_t*)P, ARG, ldp, \
-                           bias_after_pool, bn, K, pool16);                                                              \
-        GM3D_CHECK_LAUNCH();                                                                                             \
-        return GM3D_OK;                                                                                                  \
+        return launch_lds<gemm_tn_ws_kernel<KT, NW, NL, EPI, TM>>(dim3(grid), dim3(64 * (NW + NL)), lds, stream, (const bf16_t*)A, \
+                                                                  (const bf16_t*)W, bias, (bf16_t*)C, M, N, lda, ldw, ldc, tiles_n, \
+                                                                  (bf16_t*)P, ARG, ldp, bias_after_pool, bn, K, pool16);        \
     }
     // the shapes of the mini-PointNet (models_mae_learn_loss.py:872-883) and of its backward; anything else: EUNSUPPORTED
     if (P) {

@@ -228,29 +228,18 @@ template <bool GROUP>
 static int launch_knn(const float* ref, const float* query, int B, int N, int G, int k, float* dist,
                       int64_t* idx, float* nb, float* nbo, hipStream_t st) {
     const size_t lds = (size_t)N * 3 * sizeof(float);
-    if (lds > 64 * 1024) {  // only N > 5461 (validation-size clouds); idempotent, not on the step path
-        if (hipFuncSetAttribute((const void*)knn_kernel<GROUP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
-            return GM3D_ELAUNCH;
-    }
     const int qpb = knn_qpb(B, G);
     dim3 grid((G + qpb - 1) / qpb, B);
     const int use_select = 1;
     // registers hold the cloud's distances: selection by bisection (see knn_select_kernel).  Measured on MI355X: 2.0-2.5x the
     // insertion kernel at N = 1024, k = 32 (81 -> 32 us for 128 x 64 queries); at N = 2048, k = 16 (twice the registers to scan per
     // bisection step, half the insertions) the insertion kernel is 16 % faster, so longer clouds stay there unless forced (2).
-    if ((use_select && N <= 1024) || (use_select == 2 && N <= 2048)) {
-        const size_t lds2 = (((size_t)3 * N + 1) & ~(size_t)1) * sizeof(float) + 4 * 64 * sizeof(unsigned long long);
-        if (N <= 1024)
-            hipLaunchKernelGGL((knn_select_kernel<GROUP, 16>), grid, dim3(KNN_BLOCK), lds2, st, ref, query, N, G, k, dist, idx, nb, nbo, qpb);
-        else
-            hipLaunchKernelGGL((knn_select_kernel<GROUP, 32>), grid, dim3(KNN_BLOCK), lds2, st, ref, query, N, G, k, dist, idx, nb, nbo, qpb);
-        GM3D_CHECK_LAUNCH();
-        return GM3D_OK;
-    }
-    hipLaunchKernelGGL((knn_kernel<GROUP>), grid, dim3(KNN_BLOCK), lds, st, ref, query, N, G, k, dist, idx, nb, nbo, qpb);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    const bool select = (use_select && N <= 1024) || (use_select == 2 && N <= 2048);
+    if (!select) return launch_lds<knn_kernel<GROUP>>(grid, dim3(KNN_BLOCK), lds, st, ref, query, N, G, k, dist, idx, nb, nbo, qpb);
+    const size_t lds2 = (((size_t)3 * N + 1) & ~(size_t)1) * sizeof(float) + 4 * 64 * sizeof(unsigned long long);
+    if (N <= 1024)
+        return launch_lds<knn_select_kernel<GROUP, 16>>(grid, dim3(KNN_BLOCK), lds2, st, ref, query, N, G, k, dist, idx, nb, nbo, qpb);
+    return launch_lds<knn_select_kernel<GROUP, 32>>(grid, dim3(KNN_BLOCK), lds2, st, ref, query, N, G, k, dist, idx, nb, nbo, qpb);
 }
 
 }  // namespace gm3d

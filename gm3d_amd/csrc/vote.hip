@@ -206,19 +206,10 @@ extern "C" int gm3d_cls_tail_vote(const void* x, int V, int B, int T, int C, con
     if (((uintptr_t)x & 15) != 0) return GM3D_EUNSUPPORTED;     // 16-byte row loads
     const HeadArgs h{W1, b1, g1, be1, rm1, rv1, W2, b2, g2, be2, rm2, rv2, W3, b3};
     const size_t lds = (size_t)(V * 2 * TAIL_C + TAIL_TG * TAIL_C + V * TAIL_H) * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(correct);
-    if (dtype == GM3D_BF16) {
-        static LdsAttr attr;
-        if (!attr.ensure((const void*)cls_tail_vote_kernel<bf16_t>, lds)) return GM3D_ELAUNCH;
-        hipLaunchKernelGGL(cls_tail_vote_kernel<bf16_t>, dim3(B), dim3(TAIL_THREADS), lds, st, (const bf16_t*)x, V, B, T, h, cls_dim, eps,
-                           labels, mean, pred, cnt, votes);
-    } else {
-        static LdsAttr attr;
-        if (!attr.ensure((const void*)cls_tail_vote_kernel<float>, lds)) return GM3D_ELAUNCH;
-        hipLaunchKernelGGL(cls_tail_vote_kernel<float>, dim3(B), dim3(TAIL_THREADS), lds, st, (const float*)x, V, B, T, h, cls_dim, eps,
-                           labels, mean, pred, cnt, votes);
-    }
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    if (dtype == GM3D_BF16)
+        return launch_lds<cls_tail_vote_kernel<bf16_t>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const bf16_t*)x, V, B, T, h, cls_dim, eps,
+                                                        labels, mean, pred, cnt, votes);
+    return launch_lds<cls_tail_vote_kernel<float>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const float*)x, V, B, T, h, cls_dim, eps,
+                                                   labels, mean, pred, cnt, votes);
 }

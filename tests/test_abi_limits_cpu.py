@@ -136,7 +136,7 @@ LIMITS = [
     ("attention_masked_fwd.T.hd64", _mattn_fwd, 512, 513, "B", {"HD": 64}),      # guard in attention_masked.hip (f32 kernel)
     ("attention_masked_bwd.T.hd64", _mattn_bwd, 512, 513, "B", {"HD": 64}),      # guard in attention_masked.hip
     ("attention_masked_fwd.HD", lambda hd, B=1: _mattn_fwd(64, B=B, HD=hd), 64, 65, "B", {}),   # guard in attention_masked.hip
-    # bf16 keeps the head in LDS, at most 160 KiB (mattn_attr, attention_masked.hip): refused after the empty-batch return
+    # bf16 keeps the head in LDS, at most 160 KiB (launch_lds, common.hpp): refused after the empty-batch return
     ("attention_masked_fwd.T.hd64.bf16", _mattn_fwd, 480, 481, None, {"HD": 64, "dtype": 1}),
     ("attention_masked_bwd.T.hd64.bf16", _mattn_bwd, 256, 257, None, {"HD": 64, "dtype": 1}),
     ("attention_masked_bwd.T.hd32.bf16", _mattn_bwd, 480, 481, None, {"HD": 32, "dtype": 1}),
