@@ -33,6 +33,7 @@ SOURCES = {
     "gather.hip": [],
     "attention_masked.hip": [],
     "vote.hip": [],
+    "cls_tail.hip": [],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

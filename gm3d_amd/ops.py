@@ -209,6 +209,94 @@ def cls_tail_vote(x, head, labels, V, correct, votes=None):
     return mean, pred
 
 
+def _tail_head(head):
+    """cls_head_finetune (Linear, BN, ReLU, Dropout, Linear, BN, ReLU, Dropout, Linear) -> (l1, bn1, l2, bn2, l3), checked for the
+    kernels' shapes (Linear(F,256), BatchNorm1d(256) x 2 sharing eps and momentum, Linear(256,256), Linear(256,cls_dim))."""
+    l1, bn1, l2, bn2, l3 = head[0], head[1], head[4], head[5], head[8]
+    ps = [l1.weight, l1.bias, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, l2.weight, l2.bias, bn2.weight, bn2.bias,
+          bn2.running_mean, bn2.running_var, l3.weight, l3.bias]
+    for i, p in enumerate(ps):
+        _require(p, torch.float32, "head tensor %d" % i)
+    F, cls_dim = l1.weight.size(1), l3.weight.size(0)
+    want = [(256, F)] + [(256,)] * 5 + [(256, 256)] + [(256,)] * 5 + [(cls_dim, 256), (cls_dim,)]
+    if [tuple(p.shape) for p in ps] != want:
+        raise RuntimeError("head must be Linear(F,256), BN(256), ReLU, Dropout, Linear(256,256), BN(256), ReLU, Dropout, Linear(256,cls_dim)")
+    if bn1.eps != bn2.eps or bn1.momentum != bn2.momentum or bn1.momentum is None:
+        raise RuntimeError("both BatchNorm layers of the head must share eps and a (non-cumulative) momentum")
+    return l1, bn1, l2, bn2, l3
+
+
+class _ClsTail(torch.autograd.Function):
+    """gm3d_cls_tail_fwd / _bwd.  -> logits, or (logits, loss) when labels are given."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, g1, be1, W2, b2, g2, be2, W3, b3, meta):
+        bn1, bn2, mode, training, drop, labels = (meta[k] for k in ("bn1", "bn2", "mode", "training", "drop", "labels"))
+        B, T, C = x.shape
+        F, cls_dim = W1.size(1), W3.size(0)
+        dev = x.device
+        feat = torch.empty(B, F, dtype=torch.float32, device=dev)
+        argmax = torch.empty(B, C, dtype=torch.int32, device=dev)
+        h = torch.empty(2, B, 256, dtype=torch.float32, device=dev)
+        stats = torch.empty(4, 256, dtype=torch.float32, device=dev)
+        logits = torch.empty(B, cls_dim, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev) if labels is not None else None
+        _launch("gm3d_cls_tail_fwd", {"B": B, "T": T, "mode": mode, "cls_dim": cls_dim, "training": training}, lib.gm3d_cls_tail_fwd,
+                _ptr(x), B, T, C, mode, *[_ptr(p) for p in (W1, b1, g1, be1, W2, b2, g2, be2, W3, b3)], cls_dim,
+                _ptr(bn1.running_mean), _ptr(bn1.running_var), _ptr(bn1.num_batches_tracked), _ptr(bn2.running_mean),
+                _ptr(bn2.running_var), _ptr(bn2.num_batches_tracked), float(bn1.eps), float(bn1.momentum), int(training), _ptr(drop),
+                _ptr(labels), _ptr(feat), _ptr(argmax), _ptr(h), _ptr(stats), _ptr(logits), _ptr(loss), _DT[x.dtype], _stream())
+        ctx.save_for_backward(W1, g1, be1, W2, g2, be2, W3, feat, argmax, h, stats, logits, drop, labels)
+        ctx.meta = (B, T, C, mode, training, x.dtype)
+        if loss is None:
+            return logits
+        return logits, loss
+
+    @staticmethod
+    def backward(ctx, dlogits, dloss=None):
+        W1, g1, be1, W2, g2, be2, W3, feat, argmax, h, stats, logits, drop, labels = ctx.saved_tensors
+        B, T, C, mode, training, dt = ctx.meta
+        dev = feat.device
+        dlogits = dlogits.contiguous().float() if dlogits is not None else None
+        dloss = dloss.contiguous().float() if dloss is not None else None
+        ws = torch.empty(5, B, 256, dtype=torch.float32, device=dev)
+        dx = torch.empty(B, T, C, dtype=dt, device=dev)
+        grads = [torch.empty_like(p) for p in (W1, g1, g1, g1, W2, g2, g2, g2, W3)] + [torch.empty(W3.size(0), dtype=torch.float32, device=dev)]
+        dW1, db1, dg1, dbe1, dW2, db2, dg2, dbe2, dW3, db3 = grads
+        _launch("gm3d_cls_tail_bwd", {"B": B, "T": T, "mode": mode, "cls_dim": W3.size(0)}, lib.gm3d_cls_tail_bwd, B, T, C, mode,
+                *[_ptr(p) for p in (W1, g1, be1, W2, g2, be2, W3)], W3.size(0), int(training), _ptr(drop), _ptr(labels), _ptr(feat),
+                _ptr(argmax), _ptr(h), _ptr(stats), _ptr(logits), _ptr(dlogits), _ptr(dloss), _ptr(ws), _ptr(dx),
+                *[_ptr(g) for g in grads], _DT[dt], _stream())
+        return dx, dW1, db1, dg1, dbe1, dW2, db2, dg2, dbe2, dW3, db3, None
+
+
+def cls_tail(x, head, mode, training, drop=None, labels=None):
+    """The Point-M2AE classifiers' tail on our kernels (gm3d_cls_tail_fwd / _bwd: two launches each way): pool the tokens x (B,T,384)
+    f32/bf16 -- mode 0: mean + max (F = 384), mode 1: [mean ; max] (F = 768) -- then the head (nn.Sequential cls_head_finetune:
+    Linear(F,256), BN, ReLU, Dropout, Linear(256,256), BN, ReLU, Dropout, Linear(256,cls_dim)).  training: batch statistics, the
+    running statistics and num_batches_tracked updated in place, drop (2,B,256) f32 dropout factors (or None: no dropout); else the
+    running statistics and no dropout.  -> logits (B,cls_dim) f32; with labels (B,) int64 also the mean cross-entropy (a 0-d f32)."""
+    _require(x, None, "x")
+    if x.dtype not in _DT:
+        raise RuntimeError("x must be float32 or bfloat16")
+    l1, bn1, l2, bn2, l3 = _tail_head(head)
+    if x.dim() != 3 or x.size(2) != 384 or l1.weight.size(1) != (768 if mode else 384):
+        raise RuntimeError("x must be (B,T,384) and the head's input width %d for pool mode %d" % (768 if mode else 384, mode))
+    B = x.size(0)
+    if drop is not None:
+        _require(drop, torch.float32, "drop")
+        if tuple(drop.shape) != (2, B, 256):
+            raise RuntimeError("drop must be (2,B,256)")
+    if labels is not None:
+        _require(labels, torch.int64, "labels")
+        if labels.numel() != B:
+            raise RuntimeError("labels must hold B = %d entries" % B)
+    meta = {"bn1": bn1, "bn2": bn2, "mode": int(mode), "training": bool(training), "drop": drop if training else None,
+            "labels": labels}
+    return _ClsTail.apply(x, l1.weight, l1.bias, bn1.weight, bn1.bias, l2.weight, l2.bias, bn2.weight, bn2.bias, l3.weight, l3.bias,
+                          meta)
+
+
 # ------------------------------------------------------------------ KNN / grouping
 def knn(ref, query, k, return_dist=True):
     ref = ref.detach().contiguous()

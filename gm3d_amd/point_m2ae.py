@@ -324,6 +324,55 @@ def _pos(mlp, centers):
     return mlp(centers)
 
 
+def encode_levels(model, neighborhoods, centers, idxs, masks, vis_count=None, compact=False):
+    """The hierarchical encoder of `model` (its token_embed, encoder_pos_embeds, encoder_blocks and local_radius: PointM2AE and the
+    classifiers of point_m2ae_cls share it) -> per level: encoder outputs for every token position (only the visible ones are
+    meaningful).  masks: per-level bool (True = masked), or None when nothing is masked -- each level's attention mask is then the
+    radius mask alone and every level hands its encoder output on.  compact: run each level's stack in the visible-first order
+    (masked_stack.partition_visible; needs masks)."""
+    outs, prev = [], None
+    bounds = model._compact_bounds(vis_count) if compact else None
+    for i in range(3):
+        if i == 0:
+            from . import heads
+            if neighborhoods[0].is_cuda and FUSED_EMBED0 and heads._adt() == torch.bfloat16:
+                # the level-0 embed has Point-MAE's layer structure (xyz in, 16-point groups): the north-star model's fused
+                # mini-PointNet (embed.EmbedFn: analytic layer-1 statistics, BatchNorm folded into streaming passes, no
+                # concatenation, fp32 weight gradients) -- 1 M rows here, the largest tensors of the step: 53.5 -> 40.1 ms.
+                # Throughput (bf16) mode only: in fp32 the per-op modules stay, which is the path tests/test_gpu_m2ae.py pins
+                # against the oracle (the fused node's fp32 BatchNorm sums are two-stage fp32 -- within 3e-5 of the modules,
+                # tests/test_gpu_embed.py, but the oracle test's fp64 criterion for weights in front of a BatchNorm is tighter)
+                from . import embed
+                tok = embed.run_embed(model.token_embed[0], neighborhoods[0])
+            else:
+                tok = model.token_embed[0](neighborhoods[0])
+        else:
+            B, G, k = idxs[i].shape
+            from . import heads
+            tok = model.token_embed[i](heads.take_rows(prev, idxs[i].reshape(B, G * k)).view(B, G, k, -1))
+        if compact:
+            from . import masked_stack as S
+            with torch.no_grad():
+                part = S.partition_visible(masks[i], bounds[i])
+                cen_c = S.select_rows(centers[i], part["perm_c"])
+                bits = ops.radius_mask_bits(cen_c, part["vis_c"], model.local_radius[i])
+            tok_c = S.CompactFn.apply(tok, part)
+            pos = _pos(model.encoder_pos_embeds[i], cen_c)
+            y_c = model.encoder_blocks[i](tok_c, pos.to(tok_c.dtype), bits)
+            prev = S.MergeFn.apply(y_c, tok, part)            # a masked token hands on its un-encoded embedding
+            outs.append(prev)
+            continue
+        from . import heads
+        with torch.no_grad():       # == pack_mask(~(vis_i & vis_j) | radius_mask(centres)), one launch
+            bits = ops.radius_mask_bits(centers[i], None, model.local_radius[i], masked=None if masks is None else masks[i])
+        pos = _pos(model.encoder_pos_embeds[i], centers[i])
+        y = model.encoder_blocks[i](tok, pos.to(tok.dtype), bits)
+        outs.append(y)
+        # a masked token hands on its un-encoded embedding
+        prev = y if masks is None else heads.where_rows(masks[i], y, tok)
+    return outs
+
+
 class PointM2AE(nn.Module):
     """config: the `model` section of cfgs/config_Point_M2AE.yaml (dict or attribute object)."""
 
@@ -380,46 +429,7 @@ class PointM2AE(nn.Module):
     def encode(self, neighborhoods, centers, idxs, masks, vis_count=None, compact=False):
         """-> per level: encoder outputs for every token position (only the visible ones are meaningful).
         compact: run each level's stack in the visible-first order (masked_stack.partition_visible)."""
-        outs, prev = [], None
-        bounds = self._compact_bounds(vis_count) if compact else None
-        for i in range(3):
-            if i == 0:
-                from . import heads
-                if neighborhoods[0].is_cuda and FUSED_EMBED0 and heads._adt() == torch.bfloat16:
-                    # the level-0 embed has Point-MAE's layer structure (xyz in, 16-point groups): the north-star model's fused
-                    # mini-PointNet (embed.EmbedFn: analytic layer-1 statistics, BatchNorm folded into streaming passes, no
-                    # concatenation, fp32 weight gradients) -- 1 M rows here, the largest tensors of the step: 53.5 -> 40.1 ms.
-                    # Throughput (bf16) mode only: in fp32 the per-op modules stay, which is the path tests/test_gpu_m2ae.py pins
-                    # against the oracle (the fused node's fp32 BatchNorm sums are two-stage fp32 -- within 3e-5 of the modules,
-                    # tests/test_gpu_embed.py, but the oracle test's fp64 criterion for weights in front of a BatchNorm is tighter)
-                    from . import embed
-                    tok = embed.run_embed(self.token_embed[0], neighborhoods[0])
-                else:
-                    tok = self.token_embed[0](neighborhoods[0])
-            else:
-                B, G, k = idxs[i].shape
-                from . import heads
-                tok = self.token_embed[i](heads.take_rows(prev, idxs[i].reshape(B, G * k)).view(B, G, k, -1))
-            if compact:
-                from . import masked_stack as S
-                with torch.no_grad():
-                    part = S.partition_visible(masks[i], bounds[i])
-                    cen_c = S.select_rows(centers[i], part["perm_c"])
-                    bits = ops.radius_mask_bits(cen_c, part["vis_c"], self.local_radius[i])
-                tok_c = S.CompactFn.apply(tok, part)
-                pos = _pos(self.encoder_pos_embeds[i], cen_c)
-                y_c = self.encoder_blocks[i](tok_c, pos.to(tok_c.dtype), bits)
-                prev = S.MergeFn.apply(y_c, tok, part)            # a masked token hands on its un-encoded embedding
-                outs.append(prev)
-                continue
-            from . import heads
-            with torch.no_grad():       # == pack_mask(~(vis_i & vis_j) | radius_mask(centres)), one launch
-                bits = ops.radius_mask_bits(centers[i], None, self.local_radius[i], masked=masks[i])
-            pos = _pos(self.encoder_pos_embeds[i], centers[i])
-            y = self.encoder_blocks[i](tok, pos.to(tok.dtype), bits)
-            outs.append(y)
-            prev = heads.where_rows(masks[i], y, tok)              # a masked token hands on its un-encoded embedding
-        return outs
+        return encode_levels(self, neighborhoods, centers, idxs, masks, vis_count=vis_count, compact=compact)
 
     def forward(self, pts, mask=None, group=None, noaug=False, vis_count=None, prop=None):
         """pts (B,N,3) f32; mask (B,64) bool over the COARSEST tokens (True = masked; None: nothing masked).

@@ -641,6 +641,35 @@ int gm3d_cls_tail_vote(const void *x, int V, int B, int T, int C, const float *W
                        const long long *labels, float *mean, long long *pred, long long *correct, float *votes, int dtype,
                        gm3d_stream_t stream);
 
+/* ---- Classification tail of the Point-M2AE classifiers (gm3d_amd/csrc/cls_tail.hip, gm3d_amd/point_m2ae_cls.py) ---------------------
+ * gm3d_cls_tail_fwd: x (B,T,C) in `dtype` -> pooled feature feat (B,F) f32: mode 0 = mean over the tokens + max over the tokens (F = C),
+ * mode 1 = [mean ; max] (F = 2C); argmax (B,C) int32 = the token of each channel's maximum (ties -> lowest index, a NaN wins);
+ * Linear W1 (256,F) b1 -> h[0] (B,256); BatchNorm g1 / be1 -> ReLU -> times drop[0] (B,256); Linear W2 (256,256) b2 -> h[1];
+ * BatchNorm g2 / be2 -> ReLU -> times drop[1]; Linear W3 (cls_dim,256) b3 -> logits (B,cls_dim) f32.  training != 0: BatchNorm with
+ * the batch mean and biased variance, running statistics rm <- (1 - momentum) rm + momentum mean, rv <- (1 - momentum) rv +
+ * momentum var B / (B - 1), *nbt += 1; training == 0: the running statistics, no dropout, nothing written to rm / rv / nbt.
+ * drop (2,B,256) f32 dropout factors (0 or 1 / (1 - p)) or NULL (factor 1).  stats (4,256) f32 receives the mean and 1 / sqrt(var + eps)
+ * of both BatchNorms; feat, argmax, h and stats are what gm3d_cls_tail_bwd reads.  labels (B) int64 or NULL: loss (1) f32 = mean
+ * cross-entropy of the logits (a label outside [0, cls_dim) gives NaN).  Two launches.
+ *
+ * gm3d_cls_tail_bwd: the gradients of the same computation from dlogits (B,cls_dim) f32 and / or dloss (1) f32 (the cross-entropy's;
+ * needs labels), either may be NULL.  dx (B,T,C) in `dtype`: dmean / T on every token + dmax on the argmax token.  dW1 (256,F), db1,
+ * dg1, dbe1, dW2 (256,256), db2, dg2, dbe2, dW3 (cls_dim,256), db3 in f32, every sum in a fixed order without float atomics (a graph
+ * replay equals an eager call bit for bit).  ws: 5 * B * 256 f32 of scratch.  `training` and `drop` as in the forward.  Two launches.
+ *
+ * Limits: C == 384, 1 <= T <= 512, B <= 128 (B >= 2 in training), 1 <= cls_dim <= 256, mode 0 or 1; W2 and W3 16-byte aligned.
+ * B == 0 returns GM3D_OK after the shape checks, launching nothing. */
+int gm3d_cls_tail_fwd(const void *x, int B, int T, int C, int mode, const float *W1, const float *b1, const float *g1, const float *be1,
+                      const float *W2, const float *b2, const float *g2, const float *be2, const float *W3, const float *b3, int cls_dim,
+                      float *rm1, float *rv1, long long *nbt1, float *rm2, float *rv2, long long *nbt2, float eps, float momentum,
+                      int training, const float *drop, const long long *labels, float *feat, int *argmax, float *h, float *stats,
+                      float *logits, float *loss, int dtype, gm3d_stream_t stream);
+int gm3d_cls_tail_bwd(int B, int T, int C, int mode, const float *W1, const float *g1, const float *be1, const float *W2, const float *g2,
+                      const float *be2, const float *W3, int cls_dim, int training, const float *drop, const long long *labels,
+                      const float *feat, const int *argmax, const float *h, const float *stats, const float *logits,
+                      const float *dlogits, const float *dloss, float *ws, void *dx, float *dW1, float *db1, float *dg1, float *dbe1,
+                      float *dW2, float *db2, float *dg2, float *dbe2, float *dW3, float *db3, int dtype, gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
