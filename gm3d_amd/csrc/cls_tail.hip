@@ -2,6 +2,7 @@
 // Linear / BatchNorm (training or eval) / ReLU / Dropout x 2 + Linear, and the mean cross-entropy, forward in two launches and
 // backward in two.  Every sum runs in a fixed order in one thread (or a fixed butterfly in one wave): no float atomics, so a
 // graph replay reproduces an eager call bit for bit.  See include/gm3d.h for the contracts.
+#include "cls_pool.hpp"
 #include "common.hpp"
 
 using namespace gm3d;
@@ -37,24 +38,11 @@ __global__ __launch_bounds__(POOL_THREADS) void cls_pool_l1_kernel(const T* __re
     const int F = mode ? 2 * CT_C : CT_C;
     const T* xb = x + (size_t)b * T_ * CT_C;
     for (int c = tid; c < CT_C; c += POOL_THREADS) {
-        float s = 0.0f, m = ld(xb + c);
-        int am = 0;
-        for (int t = 0; t < T_; ++t) {
-            const float v = ld(xb + (size_t)t * CT_C + c);
-            s += v;
-            if (v > m || (v != v && m == m)) {
-                m = v;
-                am = t;
-            }
-        }
-        const float mean = s / (float)T_;
-        argmax[(size_t)b * CT_C + c] = am;
-        if (mode) {
-            f[c] = mean;
-            f[CT_C + c] = m;
-        } else {
-            f[c] = mean + m;
-        }
+        PoolAcc p;
+        p.init(ld(xb + c));
+        for (int t = 0; t < T_; ++t) p.add(ld(xb + (size_t)t * CT_C + c), t);
+        argmax[(size_t)b * CT_C + c] = p.am;
+        pool_feature(f, CT_C, c, mode, p.mean(T_), p.m);
     }
     __syncthreads();
     for (int k = tid; k < F; k += POOL_THREADS) feat[(size_t)b * F + k] = f[k];

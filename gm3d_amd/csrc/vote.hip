@@ -1,6 +1,7 @@
 // Voting evaluation of the fine-tuned classifier (Point-MAE_SA3D/tools/runner_finetune.py:271-335 validate_vote, :399-461
 // test_vote): the V vote clouds of a batch built in one launch, and the eval-mode classification head + vote mean + argmax +
 // correct count in one launch.  See include/gm3d.h for the contracts.
+#include "cls_pool.hpp"
 #include "common.hpp"
 
 using namespace gm3d;
@@ -176,6 +177,89 @@ __global__ __launch_bounds__(TAIL_THREADS) void cls_tail_vote_kernel(const T* __
     }
 }
 
+constexpr int POOL_MAX_T = 512;
+
+// The same head and vote epilogue for the Point-M2AE classifiers (gm3d_amd/point_m2ae_cls.py): the feature of every vote is the
+// pooling of cls_pool_l1_kernel (cls_pool.hpp) -- mode 0: mean + max (F = 384), mode 1: [mean ; max] (F = 768) -- bit for bit.
+// One workgroup per cloud b.  A thread pools 8 adjacent channels of one vote (one 16-byte row load per token); each channel's sum
+// still runs over t = 0..T-1 in order.  featout (V*B,F), when given, receives the pooled features (row v*B+b, like x).
+template <class T>
+__global__ __launch_bounds__(TAIL_THREADS) void cls_tail_vote_pool_kernel(const T* __restrict__ x, int V, int B, int T_, int mode,
+                                                                          HeadArgs h, int cls_dim, float eps,
+                                                                          const long long* __restrict__ labels, float* __restrict__ mean,
+                                                                          long long* __restrict__ pred,
+                                                                          unsigned long long* __restrict__ correct,
+                                                                          float* __restrict__ votes, float* __restrict__ featout) {
+    extern __shared__ float lds[];
+    const int F = mode ? 2 * TAIL_C : TAIL_C;
+    float* feat = lds;                                  // V x F, later V x 256 (second hidden layer), later the vote mean
+    float* hid = feat + V * F;                          // V x 256: first hidden layer, later the logits
+    const int b = blockIdx.x, tid = threadIdx.x;
+
+    for (int i = tid; i < V * TAIL_C8; i += TAIL_THREADS) {
+        const int v = i / TAIL_C8, c8 = i - v * TAIL_C8;
+        const T* xr = x + ((size_t)v * B + b) * (size_t)T_ * TAIL_C + c8 * 8;
+        float r[8];
+        PoolAcc p[8];
+        V8<T>::load(xr, r);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) p[k].init(r[k]);
+#pragma unroll 4   // several row loads in flight; the adds stay in token order
+        for (int t = 0; t < T_; ++t) {
+            V8<T>::load(xr + (size_t)t * TAIL_C, r);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) p[k].add(r[k], t);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pool_feature(feat + v * F, TAIL_C, c8 * 8 + k, mode, p[k].mean(T_), p[k].m);
+    }
+    __syncthreads();
+    if (featout)
+        for (int i = tid; i < V * F; i += TAIL_THREADS) {
+            const int v = i / F;
+            featout[((size_t)v * B + b) * F + (i - v * F)] = feat[i];
+        }
+
+    // Linear F->256, BN, ReLU, (Dropout = identity), Linear 256->256, BN, ReLU, (Dropout), Linear 256->cls_dim
+    if (mode)
+        dense<2 * TAIL_C>(h.W1, h.b1, h.g1, h.be1, h.rm1, h.rv1, eps, TAIL_H, feat, hid, V);
+    else
+        dense<TAIL_C>(h.W1, h.b1, h.g1, h.be1, h.rm1, h.rv1, eps, TAIL_H, feat, hid, V);
+    __syncthreads();
+    dense<TAIL_H>(h.W2, h.b2, h.g2, h.be2, h.rm2, h.rv2, eps, TAIL_H, hid, feat, V);
+    __syncthreads();
+    dense<TAIL_H>(h.W3, h.b3, nullptr, nullptr, nullptr, nullptr, eps, cls_dim, feat, hid, V);
+    __syncthreads();
+
+    // vote mean, argmax and count: the epilogue of cls_tail_vote_kernel (restated, that kernel stays as the Point-MAE tests pin it)
+    float* mrow = feat;
+    for (int o = tid; o < cls_dim; o += TAIL_THREADS) {
+        float s = 0.0f;
+        for (int v = 0; v < V; ++v) {
+            const float l = hid[v * TAIL_H + o];
+            if (votes) votes[((size_t)v * B + b) * cls_dim + o] = l;
+            s += l;
+        }
+        s = s / (float)V;
+        mean[(size_t)b * cls_dim + o] = s;
+        mrow[o] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {                                     // argmax, ties -> lowest index, NaN wins (torch.max)
+        int best = 0;
+        float bv = mrow[0];
+        for (int o = 1; o < cls_dim; ++o) {
+            const float l = mrow[o];
+            if (bv == bv && (l > bv || l != l)) {
+                bv = l;
+                best = o;
+            }
+        }
+        pred[b] = best;
+        if ((long long)best == labels[b]) atomicAdd(correct, 1ull);
+    }
+}
+
 }  // namespace
 
 extern "C" int gm3d_vote_sample(const float* points, const int32_t* fps_idx, const long long* subsets, const float* scale,
@@ -212,4 +296,29 @@ extern "C" int gm3d_cls_tail_vote(const void* x, int V, int B, int T, int C, con
                                                         labels, mean, pred, cnt, votes);
     return launch_lds<cls_tail_vote_kernel<float>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const float*)x, V, B, T, h, cls_dim, eps,
                                                    labels, mean, pred, cnt, votes);
+}
+
+extern "C" int gm3d_cls_tail_vote_pool(const void* x, int V, int B, int T, int C, int mode, const float* W1, const float* b1,
+                                       const float* g1, const float* be1, const float* rm1, const float* rv1, const float* W2,
+                                       const float* b2, const float* g2, const float* be2, const float* rm2, const float* rv2,
+                                       const float* W3, const float* b3, int cls_dim, float eps, const long long* labels, float* mean,
+                                       long long* pred, long long* correct, float* votes, float* feat, int dtype, gm3d_stream_t stream) {
+    if (V < 1 || B < 0 || T < 1 || cls_dim < 1) return GM3D_EINVAL;
+    if (C != TAIL_C || T > POOL_MAX_T || cls_dim > TAIL_H || V > VOTE_MAX_V || (mode != 0 && mode != 1) ||
+        (dtype != GM3D_F32 && dtype != GM3D_BF16))
+        return GM3D_EUNSUPPORTED;
+    if (B == 0) return GM3D_OK;
+    if (!x || !W1 || !b1 || !g1 || !be1 || !rm1 || !rv1 || !W2 || !b2 || !g2 || !be2 || !rm2 || !rv2 || !W3 || !b3 || !labels ||
+        !mean || !pred || !correct)
+        return GM3D_EINVAL;
+    if (((uintptr_t)x & 15) != 0) return GM3D_EUNSUPPORTED;     // 16-byte row loads
+    const HeadArgs h{W1, b1, g1, be1, rm1, rv1, W2, b2, g2, be2, rm2, rv2, W3, b3};
+    const int F = mode ? 2 * TAIL_C : TAIL_C;
+    const size_t lds = (size_t)(V * F + V * TAIL_H) * sizeof(float);     // 64 KiB at V = 16, F = 768
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(correct);
+    if (dtype == GM3D_BF16)
+        return launch_lds<cls_tail_vote_pool_kernel<bf16_t>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const bf16_t*)x, V, B, T, mode, h,
+                                                             cls_dim, eps, labels, mean, pred, cnt, votes, feat);
+    return launch_lds<cls_tail_vote_pool_kernel<float>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const float*)x, V, B, T, mode, h,
+                                                        cls_dim, eps, labels, mean, pred, cnt, votes, feat);
 }

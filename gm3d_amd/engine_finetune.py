@@ -308,16 +308,37 @@ def evaluate(data_loader, model, device, npoints=1024, bf16=True):
 # each a host-drawn subset of the FPS order shared by the batch, the test transform PointcloudScaleAndTranslate drawn per cloud,
 # and an eval forward; the mean of the vote logits decides.  Here the host makes exactly the reference's np.random calls, in its
 # order, before anything is launched; then ONE launch builds all V*B vote clouds, ONE forward runs them (split into chunks of
-# `max_clouds`), and ONE launch computes the head of every vote, the vote mean, the argmax and the correct count.
+# `max_clouds`), and ONE launch computes the head of every vote, the vote mean, the argmax and the correct count.  That last
+# launch pools the tokens the way the model does (vote_tail): PointTransformer [cls ; max] (ops.cls_tail_vote), the Point-M2AE
+# classifiers mean + max or [mean ; max] (ops.cls_tail_vote_pool).
 
 DEFAULT_VOTE_MAX_CLOUDS = 512     # clouds per forward_tokens call: B=32 x 10 votes fits in one
 
 
-def vote_point_all(npoints, n0):
-    """point_all of the vote sampling (P/tools/runner_finetune.py:284-294): POINT_ALL[npoints], capped at the cloud size."""
+def _check_npoints(npoints):
     if npoints not in POINT_ALL:
         raise NotImplementedError("npoints %d" % npoints)
+
+
+def vote_point_all(npoints, n0):
+    """point_all of the vote sampling (P/tools/runner_finetune.py:284-294): POINT_ALL[npoints], capped at the cloud size."""
+    _check_npoints(npoints)
     return min(POINT_ALL[npoints], n0)
+
+
+def vote_tail(model):
+    """The one-launch eval head + vote mean for `model`'s pooling -> fn(x, labels, V, correct, votes=None) -> (mean, pred):
+    PointTransformer -> ops.cls_tail_vote ([x[:, 0] ; max]); a Point-M2AE classifier -> ops.cls_tail_vote_pool with
+    POOL_MODES[model.pool].  Any other model raises TypeError: a tail that pools differently from the model must not run."""
+    from .point_m2ae_cls import POOL_MODES, PointM2AEClassifier
+    from .point_transformer import PointTransformer
+    head = getattr(model, "cls_head_finetune", None)
+    if isinstance(model, PointTransformer):
+        return lambda x, labels, V, correct, votes=None: ops.cls_tail_vote(x, head, labels, V, correct, votes=votes)
+    if isinstance(model, PointM2AEClassifier):
+        mode = POOL_MODES[model.pool]
+        return lambda x, labels, V, correct, votes=None: ops.cls_tail_vote_pool(x, head, mode, labels, V, correct, votes=votes)
+    raise TypeError("voting evaluation supports PointTransformer and the Point-M2AE classifiers, not %s" % type(model).__name__)
 
 
 def draw_votes(rng, point_all, npoints, times, B):
@@ -363,8 +384,10 @@ class _VoteDraws:
 
 def vote_batch(model, points, labels, subsets, scale, shift, point_all, correct, bf16=True, max_clouds=None, votes=None):
     """The votes of one batch on the device, no host sync: FPS (B,N0,3) -> point_all, vote_sample -> (V*B,npoints,3),
-    forward_tokens in chunks of `max_clouds` clouds, cls_tail_vote.  The model must be in eval mode (callers: validate_vote,
-    GraphedVoteEval).  correct: int64 device counter (+= correct predictions).  -> (mean logits (B,cls_dim), pred (B,))."""
+    forward_tokens in chunks of `max_clouds` clouds, the model's vote tail (vote_tail; TypeError before any launch for a model it
+    does not know).  The model must be in eval mode (callers: validate_vote, GraphedVoteEval).  correct: int64 device counter
+    (+= correct predictions).  -> (mean logits (B,cls_dim), pred (B,))."""
+    tail = vote_tail(model)
     V = subsets.size(0)
     fps_idx = ops.furthest_point_sample(points, point_all)
     pts = ops.vote_sample(points, fps_idx, subsets, scale, shift)
@@ -374,12 +397,12 @@ def vote_batch(model, points, labels, subsets, scale, shift, point_all, correct,
             x = model.forward_tokens(pts)
         else:
             x = torch.cat([model.forward_tokens(pts[i:i + chunk]) for i in range(0, pts.size(0), chunk)], dim=0)
-    return ops.cls_tail_vote(x.contiguous(), model.cls_head_finetune, labels, V, correct, votes=votes)
+    return tail(x.contiguous(), labels, V, correct, votes=votes)
 
 
 class GraphedVoteEval:
     """The votes of one batch shape captured once as a hipGraph: FPS -> vote_sample -> forward_tokens over V*B clouds ->
-    cls_tail_vote.  Static inputs: points, labels, subsets, scale and shift (the draws are made on the host per call and copied
+    the model's vote tail.  Static inputs: points, labels, subsets, scale and shift (the draws are made on the host per call and copied
     in); outputs `mean` (B,cls_dim), `pred` (B,), `votes` (V,B,cls_dim) when keep_votes, and the running int64 count `correct`.
     A call copies, stages the draws and replays: no host sync.
 
@@ -394,6 +417,7 @@ class GraphedVoteEval:
         B, N0 = example_points.shape[:2]
         self.npoints, self.times, self.bf16, self.rng, self.max_clouds = npoints, times, bf16, rng, max_clouds
         self.point_all = vote_point_all(npoints, N0)
+        vote_tail(self.model)
         dev = example_points.device
         self.points = example_points.detach().float().contiguous().clone()
         self.labels = example_labels.detach().reshape(-1).to(dev, torch.long).clone()
@@ -452,6 +476,8 @@ def validate_vote(model, data_loader, device, npoints=1024, times=10, bf16=True,
     One host sync per call, at the end.  Predictions and labels are gathered across ranks like the reference.
     -> {"acc_vote", "n"}; outputs=True adds the local "pred" (n,), "mean" (n,cls_dim) and "votes" (V,n,cls_dim)."""
     raw = model.module if hasattr(model, "module") else model
+    _check_npoints(npoints)
+    vote_tail(raw)
     was = raw.training
     raw.eval()
     try:

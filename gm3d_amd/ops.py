@@ -297,6 +297,49 @@ def cls_tail(x, head, mode, training, drop=None, labels=None):
                           meta)
 
 
+def cls_tail_vote_pool(x, head, mode, labels, V, correct, votes=None, feat=None):
+    """cls_tail_vote for the Point-M2AE classifiers (gm3d_cls_tail_vote_pool, one launch): the tokens x (V*B,T,384) f32/bf16 of all V
+    votes pooled like cls_tail -- mode 0: mean + max (F = 384), mode 1: [mean ; max] (F = 768), bit for bit -- then the eval-mode
+    head (cls_head_finetune with Linear(F,256); parameters and running statistics read on every call), the vote mean and its argmax.
+    labels (B,) int64; correct: int64 device counter (+= correct predictions).  votes: optional (V,B,cls_dim) f32 output; feat:
+    optional (V*B,F) f32 output of the pooled features.  -> (mean logits (B,cls_dim) f32, pred (B,) int64)."""
+    _require(x, None, "x")
+    if x.dtype not in _DT:
+        raise RuntimeError("x must be float32 or bfloat16")
+    _require(labels, torch.int64, "labels")
+    _require(correct, torch.int64, "correct")
+    if mode not in (0, 1):
+        raise RuntimeError("pool mode must be 0 (mean + max) or 1 ([mean ; max])")
+    l1, bn1, l2, bn2, l3 = _tail_head(head)
+    F = 768 if mode else 384
+    if l1.weight.size(1) != F:
+        raise RuntimeError("pool mode %d needs a head of input width %d, not %d" % (mode, F, l1.weight.size(1)))
+    if x.dim() != 3 or x.size(2) != 384 or x.size(0) % V:
+        raise RuntimeError("x must be (V*B,T,384)")
+    R, T, C = x.shape
+    B = R // V
+    cls_dim = l3.weight.size(0)
+    if labels.numel() != B:
+        raise RuntimeError("labels must hold B = %d entries" % B)
+    if votes is not None:
+        _require(votes, torch.float32, "votes")
+        if tuple(votes.shape) != (V, B, cls_dim):
+            raise RuntimeError("votes must be (V,B,cls_dim)")
+    if feat is not None:
+        _require(feat, torch.float32, "feat")
+        if tuple(feat.shape) != (R, F):
+            raise RuntimeError("feat must be (V*B,F) = (%d,%d)" % (R, F))
+    mean = torch.empty(B, cls_dim, dtype=torch.float32, device=x.device)
+    pred = torch.empty(B, dtype=torch.int64, device=x.device)
+    _launch("gm3d_cls_tail_vote_pool", {"V": V, "B": B, "T": T, "mode": mode, "cls_dim": cls_dim}, lib.gm3d_cls_tail_vote_pool,
+            _ptr(x), int(V), B, T, C, int(mode), *[_ptr(p) for p in (l1.weight, l1.bias, bn1.weight, bn1.bias, bn1.running_mean,
+                                                                     bn1.running_var, l2.weight, l2.bias, bn2.weight, bn2.bias,
+                                                                     bn2.running_mean, bn2.running_var, l3.weight, l3.bias)],
+            cls_dim, float(bn1.eps), _ptr(labels), _ptr(mean), _ptr(pred), _ptr(correct), _ptr(votes), _ptr(feat), _DT[x.dtype],
+            _stream())
+    return mean, pred
+
+
 # ------------------------------------------------------------------ KNN / grouping
 def knn(ref, query, k, return_dist=True):
     ref = ref.detach().contiguous()

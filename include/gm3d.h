@@ -670,6 +670,23 @@ int gm3d_cls_tail_bwd(int B, int T, int C, int mode, const float *W1, const floa
                       const float *dlogits, const float *dloss, float *ws, void *dx, float *dW1, float *db1, float *dg1, float *dbe1,
                       float *dW2, float *db2, float *dg2, float *dbe2, float *dW3, float *db3, int dtype, gm3d_stream_t stream);
 
+/* ---- Voting evaluation of the Point-M2AE classifiers (gm3d_amd/csrc/vote.hip) ------------------------------------------------------
+ * gm3d_cls_tail_vote_pool: gm3d_cls_tail_vote with the Point-M2AE classifiers' pooling.  x (V*B,T,C) in `dtype` (16-byte aligned),
+ * the final-norm tokens of all V votes, vote-major (row v*B+b); feature = the pooling of gm3d_cls_tail_fwd, bit for bit: mode 0 =
+ * mean over the tokens + max over the tokens (F = C), mode 1 = [mean ; max] (F = 2C), the mean a sum over t = 0..T-1 in order
+ * then / T, the max the first maximum (a NaN wins).  The eval-mode head Linear W1 (256,F) b1, BatchNorm (g1, be1, running rm1 / rv1,
+ * eps), ReLU, Linear W2 (256,256) b2, BatchNorm (g2, be2, rm2, rv2, eps), ReLU, Linear W3 (cls_dim,256) b3 (Dropout = identity);
+ * all f32, the running statistics read on every call.  mean (B,cls_dim) f32 = sum of the votes in order v = 0..V-1, then / V;
+ * pred (B) int64 = argmax (ties -> lowest index, a NaN wins); *correct += number of b with pred[b] == labels[b] (int64, no float
+ * atomics); votes (V,B,cls_dim) f32 per-vote logits, or NULL; feat (V*B,F) f32 the pooled features, or NULL.  One launch.
+ * Limits: C == 384, 1 <= T <= 512, 1 <= V <= 16, 1 <= cls_dim <= 256, mode 0 or 1; LDS (V*F + V*256) * 4 bytes, 64 KiB at V = 16,
+ * F = 768.  B == 0 returns GM3D_OK after the shape checks, launching nothing. */
+int gm3d_cls_tail_vote_pool(const void *x, int V, int B, int T, int C, int mode, const float *W1, const float *b1, const float *g1,
+                            const float *be1, const float *rm1, const float *rv1, const float *W2, const float *b2, const float *g2,
+                            const float *be2, const float *rm2, const float *rv2, const float *W3, const float *b3, int cls_dim,
+                            float eps, const long long *labels, float *mean, long long *pred, long long *correct, float *votes,
+                            float *feat, int dtype, gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
