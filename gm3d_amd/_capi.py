@@ -145,6 +145,10 @@ SIGNATURES = {
     "gm3d_cls_tail_fwd": [_vp, _i, _i, _i, _i] + [_vp] * 10 + [_i] + [_vp] * 6 + [_f, _f, _i] + [_vp] * 8 + [_i, _vp],
     "gm3d_cls_tail_bwd": [_i, _i, _i, _i] + [_vp] * 7 + [_i, _i] + [_vp] * 21 + [_i, _vp],
     "gm3d_cls_tail_vote_pool": [_vp, _i, _i, _i, _i, _i] + [_vp] * 14 + [_i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "gm3d_svm_gram": [_vp, _i, _i, _vp, _vp],
+    "gm3d_svm_smo": [_vp, _i, _i, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp],
+    "gm3d_svm_weights": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "gm3d_svm_predict": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 

@@ -34,6 +34,7 @@ SOURCES = {
     "attention_masked.hip": [],
     "vote.hip": [],
     "cls_tail.hip": [],
+    "svm.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

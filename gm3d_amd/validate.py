@@ -7,6 +7,14 @@ P/utils/dist_utils.py::gather_tensor (:50-54), SURVEY.md 8(f).1:
 Differences of execution only: FPS emits the sampled points in the same launch (no separate gather), and the token
 features are pooled on the GPU BEFORE the all-gather (the SVM never sees the un-pooled tokens), which cuts the
 collective from 64x384 to 384 floats per cloud.
+
+svm_backend="hip" solves the same SVC(C=0.01, kernel='linear') problem on the GPU (gm3d_amd.svm.LinearSVC): the gathered,
+pooled features never leave the device.  The default stays sklearn.
+
+Point-M2AE (gm3d_amd.point_m2ae.PointM2AE) is validated the same way with its own input size: FPS to 2048 points
+(Point-M2AE_SA3D/cfgs/config_Point_M2AE.yaml, npoints: 2048), then model(points, None, noaug=True), the final-normed
+coarsest tokens (B,64,384), pooled to mean + max.  That feature is stated, not pinned: the reference ships no Point-M2AE
+source (point_m2ae.py).
 """
 import numpy as np
 import torch
@@ -20,12 +28,31 @@ def fps(data, number):
     return ops.fps(data.contiguous().float(), number)[1]
 
 
-@torch.no_grad()
-def extract_features(model, points, npoints=1024, bf16=False):
-    """-> token features (B,64,384) of the eval-mode encoder (P/:427-433)."""
+MAE_NPOINTS, M2AE_NPOINTS = 1024, 2048
+
+
+def _is_m2ae(raw):
+    from .point_m2ae import PointM2AE
+    return isinstance(raw, PointM2AE)
+
+
+def default_npoints(model):
+    """The validation input size of the model: 2048 points for Point-M2AE, 1024 (the Point-MAE value) otherwise."""
     raw = model.module if hasattr(model, "module") else model
+    return M2AE_NPOINTS if _is_m2ae(raw) else MAE_NPOINTS
+
+
+@torch.no_grad()
+def extract_features(model, points, npoints=None, bf16=False):
+    """-> token features (B,64,384) of the eval-mode encoder (P/:427-433).  npoints None: default_npoints(model)."""
+    raw = model.module if hasattr(model, "module") else model
+    if npoints is None:
+        npoints = default_npoints(raw)
     pts = fps(points, npoints)      # the reference resamples unconditionally (P/main_pretrain_multi_gpu.py:430)
     assert pts.size(1) == npoints
+    if _is_m2ae(raw):
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
+            return raw(pts, None, noaug=True).float()
     mask = torch.zeros(pts.shape[0], raw.num_group, dtype=torch.bool, device=pts.device)
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
         return raw(pts, mask, noaug=True, num_visible=raw.num_group).float()
@@ -45,8 +72,13 @@ def gather_tensor(tensor, world_size=None):
     return torch.cat(outs, dim=0)
 
 
-def evaluate_svm(train_features, train_labels, test_features, test_labels):
-    """P/:476-483.  Accepts token features (n,T,C) like the reference or already pooled (n,C)."""
+def evaluate_svm(train_features, train_labels, test_features, test_labels, backend="sklearn"):
+    """P/:476-483.  Accepts token features (n,T,C) like the reference or already pooled (n,C).
+    backend "sklearn": SVC on the host (numpy or CPU inputs); "hip": gm3d_amd.svm.LinearSVC on the GPU (CUDA tensors stay there)."""
+    if backend == "hip":
+        return _evaluate_svm_hip(train_features, train_labels, test_features, test_labels)
+    if backend != "sklearn":
+        raise ValueError("unknown SVM backend %r (sklearn or hip)" % (backend,))
     from sklearn.svm import SVC
     def pooled(f):
         f = np.asarray(f)
@@ -57,10 +89,27 @@ def evaluate_svm(train_features, train_labels, test_features, test_labels):
     return np.sum(np.asarray(test_labels) == pred) * 1.0 / pred.shape[0]
 
 
+def _evaluate_svm_hip(train_features, train_labels, test_features, test_labels):
+    from .svm import LinearSVC
+
+    def dev(t, dtype):
+        t = torch.as_tensor(t)
+        return (t if t.is_cuda else t.to("cuda")).to(dtype)
+
+    def pooled(f):
+        f = dev(f, torch.float32)
+        return pool_features(f) if f.dim() == 3 else f
+    clf = LinearSVC(C=0.01).fit(pooled(train_features), dev(train_labels, torch.int64))
+    return clf.score(pooled(test_features), dev(test_labels, torch.int64))
+
+
 @torch.no_grad()
-def validate(model, extra_train_dataloader, test_dataloader, npoints=1024, device="cuda", bf16=False):
+def validate(model, extra_train_dataloader, test_dataloader, npoints=None, device="cuda", bf16=False, svm_backend="sklearn"):
     """Loaders yield (taxonomy_ids, model_ids, (points, label)) like the reference's ModelNet loaders (:428-431).
-    Returns the SVM accuracy (computed on every rank from the gathered features, like the reference)."""
+    Returns the SVM accuracy (computed on every rank from the gathered features, like the reference).  npoints None:
+    default_npoints(model).  svm_backend "hip" keeps the gathered features on the GPU and solves there."""
+    if svm_backend not in ("sklearn", "hip"):
+        raise ValueError("unknown SVM backend %r (sklearn or hip)" % (svm_backend,))
     was_training = model.training
     model.eval()
     feats = {}
@@ -72,5 +121,7 @@ def validate(model, extra_train_dataloader, test_dataloader, npoints=1024, devic
             l.append(label.view(-1))
         feats[split] = (gather_tensor(torch.cat(f, 0)), gather_tensor(torch.cat(l, 0)))
     model.train(was_training)
+    if svm_backend == "hip":
+        return evaluate_svm(feats["train"][0], feats["train"][1], feats["test"][0], feats["test"][1], backend="hip")
     return evaluate_svm(feats["train"][0].cpu().numpy(), feats["train"][1].cpu().numpy(),
                         feats["test"][0].cpu().numpy(), feats["test"][1].cpu().numpy())

@@ -687,6 +687,36 @@ int gm3d_cls_tail_vote_pool(const void *x, int V, int B, int T, int C, int mode,
                             float eps, const long long *labels, float *mean, long long *pred, long long *correct, float *votes,
                             float *feat, int dtype, gm3d_stream_t stream);
 
+/* ---- Linear-SVM validation (gm3d_amd/csrc/svm.hip) -------------------------------------------------------------------------------
+ * The solver of sklearn's SVC(C, kernel="linear") (libsvm C-SVC, one-vs-one) behind the pretraining validation,
+ * without libsvm's shrinking (it does not move the fixed point).  Training rows are grouped by class: class_start is a HOST array of
+ * ncls+1 ints, class_start[0] = 0 < class_start[1] < ... < class_start[ncls] = n (every class non-empty); class c holds the rows
+ * [class_start[c], class_start[c+1]).  Pairs p = 0..P-1, P = ncls(ncls-1)/2, run in the order (0,1), (0,2), ..., (1,2), ...; pair
+ * (s,t) sees the rows of s with y = +1, then the rows of t with y = -1, in row order, and its alpha sits in the concatenated alpha
+ * array at the sum of n_s + n_t over the pairs before it ((ncls-1)*n doubles in all).
+ * Limits: n <= 16384, d <= 1024, 2 <= ncls <= 64, n_s + n_t <= 4096 for every pair (GM3D_EUNSUPPORTED beyond, checked on the host).
+ *
+ * gm3d_svm_gram: X (n,d) f32 -> K (n,n) f64 = X X^T: f32 products are exact in f64, the sums run on v_mfma_f64_16x16x4_f64 in a
+ *   fixed order; only the lower triangle is computed and it is mirrored, so K is exactly symmetric.
+ * gm3d_svm_smo: one workgroup per pair, alpha / gradient / diag(K) in LDS as f64.  alpha = 0, G = -1; i = argmax over I_up of -yG
+ *   (Gmax); j = argmin over k in I_low with b = Gmax + y_k G_k > 0 of -b^2/a, a = K_ii + K_kk - 2 K_ik (1e-12 when a <= 0); stop when
+ *   Gmax + max over I_low of yG < tol; libsvm's clipped two-variable update; G_k += Q_ki dalpha_i + Q_kj dalpha_j, Q = yy^T K.  Ties
+ *   go to the lowest row.  I_up = {y=+1, alpha<C} u {y=-1, alpha>0}, I_low = {y=+1, alpha>0} u {y=-1, alpha<C}.  rho (P) f64 by
+ *   libsvm's rule (mean of yG over the free alpha, else the midpoint of its bounds), iters (P) int32 the updates made.  max_iter <= 0
+ *   means libsvm's cap max(10^7, 100 (n_s + n_t)); every pair that reaches the cap adds 1 to *capped (device int, not zeroed here).
+ *   LDS 24 bytes per row of the largest pair.  Bitwise reproducible.
+ * gm3d_svm_weights: w (P,d) f64, w[p] = sum over the pair's rows in order of y alpha X[row] (X the same grouped f32 rows).
+ * gm3d_svm_predict: X (m,d) f32 test rows -> pred (m) int64 = the first class with the most one-vs-one votes (pair (s,t) votes for s
+ *   when w_p . x - rho_p > 0, else for t); labels (m) int64 class indices, or NULL: *correct += the rows with pred == label (int64,
+ *   no float atomics).  One launch; m == 0 returns GM3D_OK launching nothing. */
+int gm3d_svm_gram(const float *X, int n, int d, double *K, gm3d_stream_t stream);
+int gm3d_svm_smo(const double *K, int n, int ncls, const int *class_start, double C, double tol, long long max_iter, double *alpha,
+                 double *rho, int *iters, int *capped, gm3d_stream_t stream);
+int gm3d_svm_weights(const float *X, int n, int d, int ncls, const int *class_start, const double *alpha, double *w,
+                     gm3d_stream_t stream);
+int gm3d_svm_predict(const float *X, int m, int d, int ncls, const double *w, const double *rho, const long long *labels,
+                     long long *pred, long long *correct, gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
