@@ -931,7 +931,9 @@ def run_epoch(data_loader, optimizer, device, epoch, args, eager_step, capture, 
     eager_step(samples, it) -> out dict; capture(example) -> a callable step(samples, update=) or None.
     Iterations run as hipGraph replays (what bench.py measures) once EAGER_WARMUP_ITERS eager iterations have run in this
     process -- the first iterations of the first epoch; a batch of another shape (a smaller last batch) runs eagerly.
-    Learning rate: per iteration, set only at the start of an accumulation window (P/:72-73)."""
+    Learning rate: per iteration, set only at the start of an accumulation window (P/:72-73).
+    An out dict may carry `vis_overflow` (point_m2ae's visible-first flag, (1,) int32): it is read with the finite-loss guard and
+    raises when set."""
     n_iter = len(data_loader)
     accum = getattr(args, "accum_iter", 1)
     if model_key is None:          # a weak dictionary cannot key on None: the warm-up count then belongs to the optimizer
@@ -944,6 +946,7 @@ def run_epoch(data_loader, optimizer, device, epoch, args, eager_step, capture, 
         optimizer.zero_grad()
     sums, n_upd, gsum, lr = None, 0, None, 0.0
     bad = torch.zeros((), dtype=torch.bool, device=device)
+    overflow = None
     t0, seen = time.time(), 0
     graphed, t_replay, seen_replay, n_replay, t_capture = None, 0.0, 0, 0, 0.0
     rank0 = not dist.is_initialized() or dist.get_rank() == 0
@@ -970,6 +973,8 @@ def run_epoch(data_loader, optimizer, device, epoch, args, eager_step, capture, 
         vec = torch.stack([out["loss"] + out["loss_learn"], out["loss_learn"], out["loss_mse"] * loss_scale[0],
                            out["loss_chfr"] * loss_scale[1]])
         bad |= ~torch.isfinite(vec).all()
+        if out.get("vis_overflow") is not None:
+            overflow = out["vis_overflow"]
         sums = vec if sums is None else sums + vec
         if out["grad_norm"] is not None:        # the reference's grad_norm is None on accumulation-only iterations
             g = out["grad_norm"].float().reshape(())
@@ -978,7 +983,11 @@ def run_epoch(data_loader, optimizer, device, epoch, args, eager_step, capture, 
             n_upd += 1
         seen += samples.shape[0]
         if (it + 1) % print_freq == 0 or it + 1 == n_iter:
-            if bool(bad):  # the reference exits on a non-finite loss (:173-175,185-187); one sync per print_freq
+            if bool(bad if overflow is None else bad | (overflow.reshape(-1)[0] != 0)):   # one sync per print_freq
+                if overflow is not None and int(overflow.reshape(-1)[0]) != 0:
+                    raise RuntimeError("visible-token overflow in epoch %d near iteration %d: a cloud had more visible tokens than "
+                                       "the static bound of the visible-first order (tokens were dropped)" % (epoch, it))
+                # the reference exits on a non-finite loss (:173-175,185-187)
                 raise FloatingPointError("non-finite loss in epoch %d near iteration %d" % (epoch, it))
             cur = (sums / (it + 1)).tolist() + [float(gsum) / max(n_upd, 1) if gsum is not None else 0.0]
             if log_writer is not None:

@@ -24,11 +24,13 @@ level-0 token embed runs on embed.EmbedFn, every Linear on heads.LinearBiasFn; L
 PyTorch modules.
 """
 import torch
+import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import models_mae_learn_loss as M
 from . import ops
+from . import streams
 from .hierarchical_group import HierarchicalGroup
 
 
@@ -324,12 +326,16 @@ def _pos(mlp, centers):
     return mlp(centers)
 
 
-def encode_levels(model, neighborhoods, centers, idxs, masks, vis_count=None, compact=False):
+def encode_levels(model, neighborhoods, centers, idxs, masks, vis_count=None, compact=False, cuts=None):
     """The hierarchical encoder of `model` (its token_embed, encoder_pos_embeds, encoder_blocks and local_radius: PointM2AE and the
     classifiers of point_m2ae_cls share it) -> per level: encoder outputs for every token position (only the visible ones are
     meaningful).  masks: per-level bool (True = masked), or None when nothing is masked -- each level's attention mask is then the
     radius mask alone and every level hands its encoder output on.  compact: run each level's stack in the visible-first order
-    (masked_stack.partition_visible; needs masks)."""
+    (masked_stack.partition_visible; needs masks).
+    cuts: a list to cut the autograd graph at every level's output (SegmentedM2AEStep): each level appends (its output, a detached
+    leaf of it), and the next level and the decoder read the leaf -- the backward then runs level by level (compact path only)."""
+    if cuts is not None and not compact:
+        raise NotImplementedError("the level cuts are built for the visible-first order (compact=True)")
     outs, prev = [], None
     bounds = model._compact_bounds(vis_count) if compact else None
     for i in range(3):
@@ -360,6 +366,10 @@ def encode_levels(model, neighborhoods, centers, idxs, masks, vis_count=None, co
             pos = _pos(model.encoder_pos_embeds[i], cen_c)
             y_c = model.encoder_blocks[i](tok_c, pos.to(tok_c.dtype), bits)
             prev = S.MergeFn.apply(y_c, tok, part)            # a masked token hands on its un-encoded embedding
+            if cuts is not None:
+                leaf = prev.detach().requires_grad_(True)
+                cuts.append((prev, leaf))
+                prev = leaf
             outs.append(prev)
             continue
         from . import heads
@@ -426,15 +436,16 @@ class PointM2AE(nn.Module):
         b0 = min(G[0], up(vis_count * k[2] * k[1], 32))
         return [b0, b1, b2]
 
-    def encode(self, neighborhoods, centers, idxs, masks, vis_count=None, compact=False):
+    def encode(self, neighborhoods, centers, idxs, masks, vis_count=None, compact=False, cuts=None):
         """-> per level: encoder outputs for every token position (only the visible ones are meaningful).
         compact: run each level's stack in the visible-first order (masked_stack.partition_visible)."""
-        return encode_levels(self, neighborhoods, centers, idxs, masks, vis_count=vis_count, compact=compact)
+        return encode_levels(self, neighborhoods, centers, idxs, masks, vis_count=vis_count, compact=compact, cuts=cuts)
 
-    def forward(self, pts, mask=None, group=None, noaug=False, vis_count=None, prop=None):
+    def forward(self, pts, mask=None, group=None, noaug=False, vis_count=None, prop=None, cuts=None):
         """pts (B,N,3) f32; mask (B,64) bool over the COARSEST tokens (True = masked; None: nothing masked).
         vis_count: the number of visible coarsest tokens of EVERY cloud when the caller knows it (generate_mask_ids keeps exactly
         len_keep): a static bound for the visible-first order; a wrong bound sets masked_stack.overflow_flag.
+        cuts: see encode_levels (the backward segments of SegmentedM2AEStep).
         -> dict: rec (B,256,k1,3) reconstructed level-1 patches, loss_pred (B,64), masks (per level), group, features."""
         neighborhoods, centers, idxs = group if group is not None else self.group_divider(pts)
         B = centers[0].shape[0]
@@ -442,7 +453,7 @@ class PointM2AE(nn.Module):
         if mask is None:
             mask = torch.zeros(B, self.num_group, dtype=torch.bool, device=centers[0].device)
         masks = back_project(mask, idxs)
-        enc = self.encode(neighborhoods, centers, idxs, masks, vis_count=vis_count, compact=compact)
+        enc = self.encode(neighborhoods, centers, idxs, masks, vis_count=vis_count, compact=compact, cuts=cuts)
         x2 = self.encoder_norms[2](enc[2])
         if noaug:
             return x2
@@ -489,24 +500,25 @@ class PointM2AE(nn.Module):
         return {"Chamfer_mean": loss, "matrix": matrix, "per_token": cd}
 
 
-def group_stage(divider, pts, augment=True):
+def group_stage(divider, pts, augment=True, generator=None):
     """Everything of an iteration that depends on the clouds alone -- augmentation (P/engine_pretrain.py:80), the three FPS + KNN levels,
     the token propagation's 3-NN lists -- -> (augmented clouds, (neighbourhoods, centres, idxs), (prop_idx, prop_w)).  No parameter is
-    read: GraphedM2AEStep replays this for the NEXT batch on a second stream while the current batch trains."""
+    read: GraphedM2AEStep replays this for the NEXT batch on a second stream while the current batch trains.
+    generator: the augmentation's draws come from it instead of the default generator (None: the default generator)."""
     from . import engine_pretrain as E
     with torch.no_grad():
         if augment:
-            pts = E.train_transforms(pts)
+            pts = E.train_transforms(pts, generator=generator)
         group = divider(pts)
         prop = TokenPropagation.neighbours(group[1][1], group[1][2])
     return pts, group, prop
 
 
-def pretrain_forward(model, teacher, pts, epoch, total_epoch, mask_noise=None, group=None, prop=None):
+def pretrain_forward(model, teacher, pts, epoch, total_epoch, mask_noise=None, group=None, prop=None, cuts=None):
     """One GeoMask3D iteration's forward on the hierarchical model: the EMA teacher scores the 64 coarsest tokens with nothing
     masked, the guided mask (P/models_mae_learn_loss.py:744-784 with this model's mask ratio) hides the hardest ones, the student
     reconstructs and predicts its own per-token loss.  -> dict with `loss`, `loss_chfr`, `loss_learn`, `mask`.
-    group / prop: the results of group_stage when the caller has them already."""
+    group / prop: the results of group_stage when the caller has them already; cuts: see encode_levels."""
     raw = model.module if hasattr(model, "module") else model
     with torch.no_grad():
         group = group if group is not None else teacher.group_divider(pts)
@@ -516,7 +528,7 @@ def pretrain_forward(model, teacher, pts, epoch, total_epoch, mask_noise=None, g
         mask, vis_ids, mask_ids = M.generate_mask_ids(t["loss_pred"], mask_ratio=raw.mask_ratio, guide=True, epoch=epoch,
                                                       total_epoch=total_epoch, noise=mask_noise)
         masked = mask.to(torch.bool)
-    out = model(pts, mask=masked, group=group, vis_count=vis_ids.shape[1], prop=prop)
+    out = model(pts, mask=masked, group=group, vis_count=vis_ids.shape[1], prop=prop, **({} if cuts is None else {"cuts": cuts}))
     lo = raw.forward_loss(out["rec"], group[0], group[2], out["masks"])
     pred = M.take(out["loss_pred"].float(), mask_ids)
     target = M.take(lo["matrix"].detach().float(), mask_ids)
@@ -556,6 +568,22 @@ def pretrain_step(model, model_ema, optimizer, pts, epoch, args, mask_noise=None
     return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in out.items()}
 
 
+def ddp_segment(name):
+    """Backward segment of a PointM2AE parameter, in the order the backward completes them (engine_pretrain.ddp_segment's role for
+    this model; SegmentedM2AEStep cuts the backward at every encoder level's output):
+      0  everything behind the encoder outputs: the encoder norms of levels 1-2 (they read enc[1] / enc[2] after the cut), mask token,
+         decoder stacks, token propagation, decoder positions, decoder norm, reconstruction head, loss-predictor head
+      1  level 2 (coarsest): token_embed.2, encoder_pos_embeds.2, encoder_blocks.2
+      2  level 1: the same three modules at index 1
+      3  level 0: the same three modules at index 0, and encoder_norms.0 (pretraining never reads it)"""
+    parts = name.split(".")
+    if parts[0] in ("token_embed", "encoder_pos_embeds", "encoder_blocks") and len(parts) > 1 and parts[1].isdigit():
+        return 3 - int(parts[1])
+    if parts[0] == "encoder_norms" and parts[1] == "0":
+        return 3
+    return 0
+
+
 class GraphedM2AEStep:
     """The Point-M2AE + GeoMask3D step as hipGraph replays, with the NEXT batch's grouping beside the current batch's training.
 
@@ -565,28 +593,51 @@ class GraphedM2AEStep:
     queues the next batch's grouping on the side stream and replays the training graph -- what engine_finetune.GraphedFinetuneStep does
     for its point sampling.  Without `next_pts` the grouping of a batch runs right before its training (same results: the stages read
     and write disjoint state; with augmentation on, the random draws of a batch are taken when its grouping is queued).
-    `epoch` is baked into the captures (mask schedule), like GraphedPretrainStep."""
+    `epoch` is baked into the captures (mask schedule), like GraphedPretrainStep.
+    generator: a CUDA generator of its own for the augmentation draws, registered with `group_graph` only.  The two graphs replay on
+    two streams; with both drawing from the default generator (None: today's behaviour) the Philox offsets of the augmentation and
+    of the training graph's draws (DropPath, mask noise) depend on the replay order, so look-ahead changes the draws.  With a
+    generator each stage owns its sequence and look-ahead or not gives the same trajectory."""
 
-    def __init__(self, model, model_ema, optimizer, args, example, epoch, augment=True, inject_mask_noise=False, warmup_iters=2):
-        from . import streams
+    def __init__(self, model, model_ema, optimizer, args, example, epoch, augment=True, inject_mask_noise=False, warmup_iters=2,
+                 generator=None):
         self.model, self.ema, self.opt, self.args, self.epoch, self.augment = model, model_ema, optimizer, args, epoch, augment
+        self.generator = generator
         raw = model.module if hasattr(model, "module") else model
+        dev = example.device
+        self._init_staging(example, raw, inject_mask_noise)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup_iters):
+                if generator is None:
+                    pretrain_step(model, model_ema, optimizer, self.static_in.clone(), epoch, args, mask_noise=self.static_noise, augment=augment)
+                else:
+                    staged = group_stage(model_ema.ema.group_divider, self.static_in.clone(), augment=augment, generator=generator)
+                    pretrain_step(model, model_ema, optimizer, None, epoch, args, mask_noise=self.static_noise, staged=staged)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        staged = self._capture_grouping(model_ema.ema.group_divider)
+        self.train_graph = torch.cuda.CUDAGraph()
+        with streams.capture(self.train_graph):
+            self.out = pretrain_step(model, model_ema, optimizer, None, epoch, args, mask_noise=self.static_noise, staged=staged)
+        torch.cuda.synchronize()
+
+    def _init_staging(self, example, raw, inject_mask_noise):
         dev = example.device
         self.static_in = example.clone()
         self.static_noise = torch.rand(example.shape[0], raw.num_group, device=dev) if inject_mask_noise else None
         self.side = torch.cuda.Stream(device=dev)
         self._ready, self._staged = torch.cuda.Event(), False
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup_iters):
-                pretrain_step(model, model_ema, optimizer, self.static_in.clone(), epoch, args, mask_noise=self.static_noise, augment=augment)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        divider = model_ema.ema.group_divider
+
+    def _capture_grouping(self, divider):
+        """capture `group_graph` on the side stream, replay it once (a capture executes nothing) -> the staged tuple the training
+        capture reads (clones of the grouping outputs, refreshed by one multi-tensor copy per call)."""
         self.group_graph = torch.cuda.CUDAGraph()
+        if self.generator is not None:
+            self.group_graph.register_generator_state(self.generator)
         with streams.capture(self.group_graph, stream=self.side):
-            pts, group, prop = group_stage(divider, self.static_in, augment=augment)
+            pts, group, prop = group_stage(divider, self.static_in, augment=self.augment, generator=self.generator)
             self._stage_out = [pts] + list(group[0]) + list(group[1]) + list(group[2]) + list(prop)
         torch.cuda.synchronize()
         self.group_graph.replay()            # real values for the capture below (a capture executes nothing)
@@ -594,11 +645,7 @@ class GraphedM2AEStep:
         self._train_in = [t.clone() for t in self._stage_out]
         n = len(group[0])
         ti = self._train_in
-        staged = (ti[0], (ti[1:1 + n], ti[1 + n:1 + 2 * n], ti[1 + 2 * n:1 + 3 * n]), (ti[1 + 3 * n], ti[2 + 3 * n]))
-        self.train_graph = torch.cuda.CUDAGraph()
-        with streams.capture(self.train_graph):
-            self.out = pretrain_step(model, model_ema, optimizer, None, epoch, args, mask_noise=self.static_noise, staged=staged)
-        torch.cuda.synchronize()
+        return (ti[0], (ti[1:1 + n], ti[1 + n:1 + 2 * n], ti[1 + 2 * n:1 + 3 * n]), (ti[1 + 3 * n], ti[2 + 3 * n]))
 
     def _enqueue_grouping(self, pts):
         ev = torch.cuda.Event()
@@ -611,7 +658,8 @@ class GraphedM2AEStep:
             self._ready.record(self.side)
         self._staged = True
 
-    def __call__(self, pts, mask_noise=None, next_pts=None):
+    def _take_staged(self, pts, mask_noise, next_pts):
+        """this batch's grouping -> the training graph's inputs; the next batch's grouping queued on the side stream."""
         main = torch.cuda.current_stream()
         if not self._staged:                          # first call, or no look-ahead was given last time: group this batch now
             self._enqueue_grouping(pts)
@@ -622,5 +670,167 @@ class GraphedM2AEStep:
         self._staged = False
         if next_pts is not None:                      # queued BEFORE the training graph so that the two run side by side
             self._enqueue_grouping(next_pts)
+
+    def __call__(self, pts, mask_noise=None, next_pts=None):
+        self._take_staged(pts, mask_noise, next_pts)
         self.train_graph.replay()
+        return self.out
+
+
+class SegmentedM2AEStep(GraphedM2AEStep):
+    """Data-parallel Point-M2AE step with the gradient all-reduce hidden behind backward (engine_pretrain.SegmentedDDPStep for this
+    model): the grouping graph with look-ahead of GraphedM2AEStep, then SIX hipGraphs with eager collectives between them (no
+    collective is captured):
+
+        graph 0  teacher, mask, student forward, backward of the decoder side (segment 0)  -> all-reduce (async) of segment 0
+        graph 1  backward of level 2 (segment 1)                                              -> all-reduce (async) of segment 1
+        graph 2  backward of level 1 (segment 2)                                              -> all-reduce (async) of segment 2
+        graph 3  backward of level 0 (segment 3)                                              -> all-reduce of segment 3 (+ every
+                                                                                                 non-decayed parameter)
+        graph 4  clip + AdamW + EMA (after the collectives)
+
+    The backward is cut with torch.autograd.grad at every encoder level's output (encode_levels(cuts=)).  enc[1] has two readers --
+    the level-2 token embed and the decoder's skip through encoder_norms.1 / token_prop -- so its gradient is the sum of segment 0's
+    and segment 1's contributions before segment 2 starts (the sum autograd forms in the single backward).  Each segment is its own
+    fused.async_wgrad(defer_heads=True) region: the small layers' deferred weight gradients of a segment are final when its
+    collective is issued.  Needs FlatAdamWEma built with segment_of=ddp_segment.
+    Construction broadcasts rank 0's parameters, optimizer state, EMA teacher and buffers; every call broadcasts the BatchNorm
+    buffers (DDP's broadcast_buffers).  BatchNorm batch statistics stay per rank (no SyncBN, like the reference's DDP).
+    use_graphs=False: the same segments eagerly (grouping in line, no look-ahead)."""
+
+    NSEG = 4
+
+    def __init__(self, model, model_ema, optimizer, args, example, epoch, augment=True, inject_mask_noise=False, warmup_iters=2,
+                 generator=None, process_group=None, use_graphs=True, broadcast=True):
+        from . import engine_pretrain as E
+        if getattr(args, "accum_iter", 1) > 1:
+            raise NotImplementedError("SegmentedM2AEStep runs accum_iter = 1 (config_Point_M2AE.yaml: step_per_update 1)")
+        ranges = getattr(optimizer, "segment_ranges", None)
+        if ranges is None or sorted(ranges) != list(range(self.NSEG)):
+            raise ValueError("SegmentedM2AEStep needs FlatAdamWEma built with segment_of=point_m2ae.ddp_segment "
+                             "(engine_pretrain_m2ae.build_optimizer(..., segmented=True))")
+        self.model, self.ema, self.opt, self.args, self.epoch, self.augment = model, model_ema, optimizer, args, epoch, augment
+        self.generator = generator
+        self.raw = model.module if hasattr(model, "module") else model
+        self.group = process_group
+        self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
+        self._avg = dist.is_initialized() and dist.get_backend(process_group) == "nccl" and self.world > 1   # as SegmentedDDPStep
+        if broadcast:
+            E.broadcast_state(self.raw, model_ema, optimizer, group=process_group)
+        self._init_staging(example, self.raw, inject_mask_noise)
+        views = dict((id(p), g) for p, g in optimizer.flat_grad_views())
+        self.seg_params = {sg: list(ps) for sg, ps in optimizer.segment_params.items()}
+        self.seg_views = {sg: [views[id(p)] for p in ps] for sg, ps in self.seg_params.items()}
+        self._cuts = self._grads = None
+        self.graphs = None
+        if not use_graphs:
+            return
+        if warmup_iters:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(warmup_iters):
+                    self._eager(self.static_in.clone())
+            torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        staged = self._capture_grouping(model_ema.ema.group_divider)
+        mode = "thread_local" if dist.is_initialized() else "global"
+        self.graphs = [torch.cuda.CUDAGraph() for _ in range(self.NSEG + 1)]
+        with streams.capture(self.graphs[0], capture_error_mode=mode):
+            self.out = self._segment(0, staged)
+        for k in range(1, self.NSEG):
+            with streams.capture(self.graphs[k], pool=self.graphs[0].pool(), capture_error_mode=mode):
+                self._segment(k)
+        with streams.capture(self.graphs[self.NSEG], pool=self.graphs[0].pool(), capture_error_mode=mode):
+            self.out["grad_norm"] = self._update()
+        torch.cuda.synchronize()
+
+    # ---- the four backward segments -----------------------------------------------------------------------------------------
+    def _forward(self, staged):
+        """pretrain_step's forward with the level cuts -> (outputs, the scalar loss)."""
+        from contextlib import nullcontext
+        pts, group, prop = staged
+        self.opt.zero_grad(set_to_none=True)       # no stale p.grad may be gathered over the segment gradients by step()
+        self._cuts = []
+        amp = torch.autocast("cuda", dtype=torch.bfloat16) if getattr(self.args, "bf16", False) else nullcontext()
+        with amp:
+            out = pretrain_forward(self.model, self.ema.ema, pts, self.epoch, self.args.epochs, mask_noise=self.static_noise,
+                                   group=group, prop=prop, cuts=self._cuts)
+        return out
+
+    def _segment(self, k, staged=None):
+        """segment k's backward in its own deferred-weight-gradient region, its gradients stored into their flat slots.
+        Segment 0 runs the forward first; segment k > 0 starts from the gradient of level (3 - k)'s output."""
+        from contextlib import nullcontext
+        from . import fused
+        from . import engine_pretrain as E
+        out = None
+        ps = self.seg_params[k]
+        if k == 0:
+            out = self._forward(staged)
+            roots, gouts = [out["loss"]], None
+            leaves = [self._cuts[2][1], self._cuts[1][1]]              # enc[2], enc[1] as the decoder read them
+        else:
+            lvl = self.NSEG - 1 - k                                     # segment 1 = level 2, ..., segment 3 = level 0
+            roots, gouts = [self._cuts[lvl][0]], [self._grads[lvl]]
+            leaves = [self._cuts[lvl - 1][1]] if lvl > 0 else []
+        dev = roots[0].device
+        region = fused.async_wgrad(dev, defer_heads=True) if DEFER_WGRADS and dev.type == "cuda" else nullcontext()
+        with region:
+            g = torch.autograd.grad(roots, ps + leaves, grad_outputs=gouts, allow_unused=True)
+        E.SegmentedDDPStep._store(self, k, g[:len(ps)])
+        gl = g[len(ps):]
+        if k == 0:
+            self._grads = {2: gl[0], 1: gl[1]}
+        elif lvl == 2:
+            # enc[1]'s two readers: the decoder's skip (segment 0) + the level-2 token embed (this segment) -- the sum the single
+            # backward's input buffer forms for the node that produced enc[1]
+            a, b = self._grads[1], gl[0]
+            self._grads[1] = b if a is None else (a if b is None else a + b)
+        elif lvl == 1:
+            self._grads[0] = gl[0]
+        if out is not None:
+            return {k_: (v.detach() if torch.is_tensor(v) else v) for k_, v in out.items()}
+        return None
+
+    def _update(self):
+        from . import engine_pretrain as E
+        self.opt.mark_grads_filled()
+        return E.step_update(self.model, self.ema, self.opt)
+
+    def _reduce(self, seg):
+        from . import engine_pretrain as E
+        return E.SegmentedDDPStep._reduce(self, seg)
+
+    def _wait(self, works):
+        from . import engine_pretrain as E
+        E.SegmentedDDPStep._wait(self, works)
+
+    def _run(self, phases):
+        works = []
+        for k in range(self.NSEG):
+            phases[k]()
+            works.append(self._reduce(k))
+        self._wait(works)
+
+    def _eager(self, pts):
+        staged = group_stage(self.ema.ema.group_divider, pts, augment=self.augment, generator=self.generator)
+        res = {}
+        self._run([lambda: res.update(self._segment(0, staged))] + [lambda k=k: self._segment(k) for k in range(1, self.NSEG)])
+        self._cuts = self._grads = None       # eager: let the autograd graph go (captured graphs keep theirs alive)
+        res["grad_norm"] = self._update()
+        return res
+
+    def __call__(self, pts, mask_noise=None, next_pts=None, update=True):
+        if not update:
+            raise NotImplementedError("SegmentedM2AEStep runs accum_iter = 1")
+        from . import engine_pretrain as E
+        E.broadcast_buffers(self.raw, group=self.group)      # DDP's per-forward BatchNorm-buffer broadcast from rank 0
+        if self.graphs is None:
+            if self.static_noise is not None and mask_noise is not None:
+                self.static_noise.copy_(mask_noise, non_blocking=True)
+            return self._eager(pts)
+        self._take_staged(pts, mask_noise, next_pts)
+        self._run([g.replay for g in self.graphs[:self.NSEG]])
+        self.graphs[self.NSEG].replay()
         return self.out
