@@ -31,7 +31,6 @@ SIGNATURES = {
     "gm3d_attention_qkv_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "gm3d_attention_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
     "gm3d_ln_plain_partial_rows": [_i],
-    "gm3d_ln_set_grid_cap": [_i],
     "gm3d_ln_plain_fwd": [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _vp],
     "gm3d_ln_plain_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "gm3d_residual_ln_fwd": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
@@ -80,13 +79,10 @@ SIGNATURES = {
     "gm3d_gemm_tn_bf16_lna": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "gm3d_gemm_tile_rows": [_i],
     "gm3d_gemm_tn_bf16_ring": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_ring_set_depth": [_i, _i],
     "gm3d_gemm_tn_bf16_ws": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
     "gm3d_gemm_tn_bf16_ws_pool": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "gm3d_gemm_ws_supported": [_i, _i, _i],
     "gm3d_gemm_tn_bf16_ws_poolg": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_nt_set_big_tiles": [_i],
-    "gm3d_gemm_nt_set_order": [_i],
     "gm3d_gemm_nt_bf16_sum": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _vp],
     "gm3d_gemm_nt_tiles": [_i, _i],
     "gm3d_gemm_nt_bf16_multi": [_i] + [_vp] * 14 + [_vp],
@@ -95,7 +91,6 @@ SIGNATURES = {
     "gm3d_gemm_ws_stats_rows": [_i, _i, _i],
     "gm3d_gemm_tn_bf16_ws_bn_apply_g": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
     "gm3d_gemm_tn_bf16_ws_bn_stats_g": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_ws_set_occupancy": [_i],
     "gm3d_gemm_tn_bf16_ring96": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "gm3d_gemm_tn_bf16_dma": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "gm3d_gemm_tn_bf16_dma_gelu_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
@@ -107,10 +102,11 @@ SIGNATURES = {
     "gm3d_sum_few_rows": [_vp, _i, _i, ctypes.c_longlong, _vp, _vp],
     "gm3d_gemm_nt_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i,
                           ctypes.c_longlong, _vp],
+    "gm3d_gemm_nt_bf16_big": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i,
+                              ctypes.c_longlong, _vp],
     "gm3d_gemm_nt_splits": [_i, _i, _i, _i],
     "gm3d_radius_mask_bits": [_vp, _vp, _f, _i, _i, _vp, _vp],
     "gm3d_radius_mask_bits_m": [_vp, _vp, _i, _f, _i, _i, _vp, _vp],
-    "gm3d_attention_masked_set_wide": [_i],
     "gm3d_attention_masked_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "gm3d_attention_masked_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "gm3d_mask_select": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp],

@@ -464,8 +464,6 @@ __global__ __launch_bounds__(256) void radius_mask_bits_kernel(const float* __re
     bits[((size_t)b * G + i) * W + wd] = w;
 }
 
-static int MATTN_WIDE = 1;      // 8 tiles per workgroup for HD <= 32, T > 128 (gm3d_attention_masked_set_wide: the A/B knob)
-
 static int mattn_check(const void* a, const void* b, int B, int T, int H, int HDv, int dtype) {
     if (!a || !b || B < 0 || T < 1 || H < 1) return GM3D_EINVAL;
     if (HDv != 16 && HDv != 32 && HDv != 64) return GM3D_EUNSUPPORTED;
@@ -476,11 +474,6 @@ static int mattn_check(const void* a, const void* b, int B, int T, int H, int HD
 }
 
 }  // namespace gm3d
-
-extern "C" int gm3d_attention_masked_set_wide(int on) {
-    gm3d::MATTN_WIDE = on ? 1 : 0;
-    return GM3D_OK;
-}
 
 extern "C" int gm3d_radius_mask_bits(const float* center, const unsigned char* vis, float radius, int B, int G, unsigned* bits,
                                      gm3d_stream_t stream) {
@@ -511,7 +504,7 @@ extern "C" int gm3d_attention_masked_fwd(const void* qkv, const unsigned* mask, 
     const int W = (T + 31) / 32;
     if (dtype == GM3D_BF16) {
         const int rowsK = 32 * W;
-        const int nwv = (HD <= 32 && T > 128 && MATTN_WIDE) ? 8 : 4;          // query tiles (= waves) per workgroup
+        const int nwv = (HD <= 32 && T > 128) ? 8 : 4;          // query tiles (= waves) per workgroup
         const size_t lds = (size_t)(2 * rowsK + 32 * nwv) * (HD * 2 + 16);
         const dim3 grid(B * H, (T + 32 * nwv - 1) / (32 * nwv));
 #define GM3D_MF(HD_, NWV_)                                                                                                         \
@@ -540,7 +533,7 @@ extern "C" int gm3d_attention_masked_bwd(const void* qkv, const unsigned* mask, 
     if (dtype == GM3D_BF16) {
         const int rows = 32 * W;
         const size_t lds = (size_t)4 * rows * (HD * 2 + 16) + (size_t)2 * rows * sizeof(float);
-        const int ntp = (HD <= 32 && T > 128 && MATTN_WIDE) ? 8 : 4;          // key tiles (= query tiles) per workgroup
+        const int ntp = (HD <= 32 && T > 128) ? 8 : 4;          // key tiles (= query tiles) per workgroup
         const dim3 grid(B * H, (T + 32 * ntp - 1) / (32 * ntp));
 #define GM3D_MB(HD_, NTP_)                                                                                                         \
     launch_lds<mattn_bwd_bf16_kernel<HD_, NTP_>>(grid, dim3(128 * NTP_), lds, stream, (const bf16_t*)qkv, mask, (const bf16_t*)out,        \

@@ -6,7 +6,7 @@
 //   second_conv = Conv1d(512,512) -> BatchNorm1d(512) -> ReLU -> Conv1d(512,384);  max over k
 // on rows = B*G*k = 262,144 points per step (twice: EMA teacher in eval mode, student in train mode).
 //
-// The three wide 1x1 convolutions stay plain GEMMs (hipBLASLt); everything between them is here, each as ONE
+// The three wide 1x1 convolutions are plain GEMMs (csrc/gemm*.hip through gemm.mm); everything between them is here, each as ONE
 // pass over a (group, k, C) activation with 16-byte accesses:
 //   * layer 1 (K=3) + BatchNorm + ReLU are evaluated on the fly from xyz -- the (rows,128) pre-activation never
 //     exists, and its batch statistics are analytic in the 3x3 input moments (moments3_kernel);

@@ -47,13 +47,12 @@ __device__ __forceinline__ bf16x8 nt_frag(const unsigned char* img, int kk0, int
 __device__ __forceinline__ void nt_tile(unsigned char* nsm, const bf16_t* __restrict__ Y, const bf16_t* __restrict__ X, float* __restrict__ O,
                                         int rows_split, int ldy, int ldx, int ldo, long long sY, long long sX, long long sO, long long sOs,
                                         int splits, int tiles_n, int tiles_k, int logical, int Nfull, int Kfull, int* __restrict__ counters,
-                                        float* __restrict__ Ofin, long long sOfin, int ldofin, int tn_fastest = 0) {
+                                        float* __restrict__ Ofin, long long sOfin, int ldofin) {
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
     int t = logical;
-    int tk, tn;
-    if (tn_fastest) { tn = t % tiles_n; t /= tiles_n; tk = t % tiles_k; t /= tiles_k; }     // measurement knob (gm3d_gemm_nt_set_order)
-    else { tk = t % tiles_k; t /= tiles_k; tn = t % tiles_n; t /= tiles_n; }
+    const int tk = t % tiles_k; t /= tiles_k;
+    const int tn = t % tiles_n; t /= tiles_n;
     const int sp = t % splits;
     const int b = t / splits;
     const int n0 = tn * 128, k0 = tk * 128;
@@ -197,7 +196,6 @@ struct NtProblem {
 constexpr int NT_MAXP = 16;
 struct NtMulti {
     int count;
-    int tn_fastest;
     NtProblem p[NT_MAXP];
 };
 
@@ -214,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_multi_kernel(NtMulti m) {
     const int logical = (local & 7) * per_xcd + (local >> 3);
     if (logical >= q.total) return;
     nt_tile(nsm, q.Y, q.X, q.O, q.rows_split, q.ldy, q.ldx, q.ldo, q.sY, q.sX, q.sO, q.sOs, q.splits, q.tiles_n, q.tiles_k, logical, q.N, q.K,
-            nullptr, nullptr, 0, 0, m.tn_fastest);
+            nullptr, nullptr, 0, 0);
 }
 
 // ---- 128 x 384 output tiles (the block stacks' weight gradients: every (N, K) there is a multiple of (128, 384)) ----------------------
@@ -363,28 +361,15 @@ __global__ __launch_bounds__(512, 1) void gemm_nt384_bf16_kernel(const bf16_t* _
 
 }  // namespace gm3d
 
-// measurement knob: 0 (default) = 128 x 128 tiles everywhere, 1 = 128 x 384 tiles where the shape is a multiple of them.
+// The products run 128 x 128 tiles everywhere; the 128 x 384 kernel is reached through gm3d_gemm_nt_bf16_big alone.
 // Measured (tools/wgrad_tiles.py, kernel only, MI355X): the big tiles reach 530 TFLOP/s where the 128 x 128 kernel reaches 620-790 at
 // the splits the step uses (three 48 KiB workgroups per CU keep more L2 -> LDS bytes in flight than one 96 KiB workgroup does; a
-// 192 x 384 / 8-wave form without the software pipeline reached 800-820 at 8 splits, i.e. with twice the slab-sum traffic) -> off.
-static int NT_BIG_TILES = 0;
-extern "C" int gm3d_gemm_nt_set_big_tiles(int on) {
-    NT_BIG_TILES = on ? 1 : 0;
-    return GM3D_OK;
-}
-static bool nt_big(int N, int K) { return NT_BIG_TILES && N % 128 == 0 && K % 384 == 0; }
+// 192 x 384 / 8-wave form without the software pipeline reached 800-820 at 8 splits, i.e. with twice the slab-sum traffic).
 
 extern "C" int gm3d_gemm_nt_splits(int batch, int R, int N, int K) {
     // the smallest power-of-two row split (<= 64, gm3d_sum_few_rows' limit) that offers the chip >= 400 workgroups (tools/wgrad_split_sweep.py: the optimum sits at 400-600) while every
     // split keeps >= 512 rows (16 stages)
     if (batch < 1 || R < 1 || N < 1 || K < 1) return 1;
-    if (nt_big(N, K)) {
-        // one 512-thread workgroup per CU: the smallest split that offers >= 224 of them, every split >= 256 rows (8 stages)
-        const long long tiles = (long long)batch * (N / 128) * (K / 384);
-        int s = 1;
-        while (tiles * s < 224 && s < 64 && R % (64 * s) == 0 && R / (2 * s) >= 256) s *= 2;
-        return s;
-    }
     const long long tiles = (long long)batch * ((N + 127) / 128) * ((K + 127) / 128);
     int s = 1;
     while (tiles * s < 400 && s < 64 && R % (64 * s) == 0 && R / (2 * s) >= 512) s *= 2;
@@ -393,15 +378,16 @@ extern "C" int gm3d_gemm_nt_splits(int batch, int R, int N, int K) {
 
 static int nt_launch(const void* dY, const void* X, float* out, int batch, int R, int N, int K, int ldy, int ldx, int ldo,
                      long long stride_y, long long stride_x, long long stride_o, int splits, long long stride_split, gm3d_stream_t stream,
-                     int* counters, float* fin, long long stride_fin, int ldfin) {
+                     int* counters, float* fin, long long stride_fin, int ldfin, bool big = false) {
     using namespace gm3d;
     if (!dY || !X || !out || batch < 0 || R < 1 || N < 1 || K < 1 || splits < 1) return GM3D_EINVAL;
     if (N % 8 || K % 8 || ldy % 8 || ldx % 8 || ldy < N || ldx < K || ldo < K) return GM3D_EUNSUPPORTED;   // ragged N / K: multiples of 8
+    if (big && (N % 128 || K % 384)) return GM3D_EUNSUPPORTED;      // whole 128 x 384 tiles only
     if (R % (NT_BR * splits)) return GM3D_EUNSUPPORTED;
     if (((size_t)dY | (size_t)X) & 15) return GM3D_EUNSUPPORTED;
     if (splits > 1 && stride_split < (long long)N * ldo) return GM3D_EINVAL;
     if (batch == 0) return GM3D_OK;
-    if (!counters && nt_big(N, K)) {
+    if (big) {
         const long long total = (long long)batch * splits * (N / 128) * (K / 384);
         if (total > 0x7ffffff0LL) return GM3D_EUNSUPPORTED;
         const int grid = (int)((total + 7) / 8 * 8);
@@ -425,6 +411,14 @@ extern "C" int gm3d_gemm_nt_bf16(const void* dY, const void* X, float* out, int 
                                  gm3d_stream_t stream) {
     return nt_launch(dY, X, out, batch, R, N, K, ldy, ldx, ldo, stride_y, stride_x, stride_o, splits, stride_split, stream, nullptr, nullptr, 0,
                      0);
+}
+
+// the same product on 128 x 384 tiles: N % 128 == 0 and K % 384 == 0, else GM3D_EUNSUPPORTED.  Bit-identical to gm3d_gemm_nt_bf16 for equal splits.
+extern "C" int gm3d_gemm_nt_bf16_big(const void* dY, const void* X, float* out, int batch, int R, int N, int K, int ldy, int ldx, int ldo,
+                                     long long stride_y, long long stride_x, long long stride_o, int splits, long long stride_split,
+                                     gm3d_stream_t stream) {
+    return nt_launch(dY, X, out, batch, R, N, K, ldy, ldx, ldo, stride_y, stride_x, stride_o, splits, stride_split, stream, nullptr, nullptr, 0,
+                     0, true);
 }
 
 // ... with the sum over the row splits inside the launch: part (batch, splits, N, K) f32 scratch for the slabs, out (batch, N, ldo) the
@@ -477,12 +471,6 @@ __global__ __launch_bounds__(256) void nt_sum_multi_kernel(NtSumMulti m) {
 // that adds the row-split slabs of every problem with splits > 1 (part[j]: (batch, splits, N, K) f32 scratch; out[j]: (batch, N, K)
 // contiguous rows of K, batch stride stride_o[j]).  Problems with splits == 1 write out[j] directly.  Results are bit-identical to the
 // separate launches (same tiles, same slab order).
-static int NT_MULTI_TN_FASTEST = 0;
-extern "C" int gm3d_gemm_nt_set_order(int tn_fastest) {
-    NT_MULTI_TN_FASTEST = tn_fastest ? 1 : 0;
-    return GM3D_OK;
-}
-
 extern "C" int gm3d_gemm_nt_bf16_multi(int count, const void* const* dY, const void* const* X, float* const* out, float* const* part,
                                        const int* batch, const int* R, const int* N, const int* K, const int* ldy, const int* ldx,
                                        const long long* stride_y, const long long* stride_x, const long long* stride_o, const int* splits,
@@ -494,7 +482,6 @@ extern "C" int gm3d_gemm_nt_bf16_multi(int count, const void* const* dY, const v
     NtMulti m;
     NtSumMulti sm;
     m.count = count;
-    m.tn_fastest = NT_MULTI_TN_FASTEST;
     sm.count = 0;
     long long first = 0;
     int max_batch = 1;

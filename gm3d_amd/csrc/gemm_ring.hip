@@ -305,16 +305,9 @@ __global__ __launch_bounds__(192) void gemm_tn_ring96_kernel(const bf16_t* __res
 
 }  // namespace gm3d
 
-// K-stages in flight ahead of the multiplied one, per tile height (64, 128); gm3d_gemm_ring_set_depth is the measurement knob of
-// tools/gemm_kbench.py (values outside the supported range are clamped)
-static int RING_DEPTH[2] = {2, 2};
-
-extern "C" int gm3d_gemm_ring_set_depth(int bm, int depth) {
-    if (bm != 64 && bm != 128) return GM3D_EINVAL;
-    const int hi = bm == 64 ? 4 : 3;
-    RING_DEPTH[bm == 64 ? 0 : 1] = depth < 2 ? 2 : (depth > hi ? hi : depth);
-    return GM3D_OK;
-}
+// K-stages in flight ahead of the multiplied one, for both tile heights and both epilogues (deeper rings measured no faster:
+// profiles/NEGATIVE_RESULTS.md); the kernel instantiation and the LDS size both come from this one name
+static constexpr int RING_DEPTH = 2;
 
 static int ring_launch(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int lda, int ldw, int ldc, int bm,
                        gm3d_stream_t stream, const float* res, const float* rowscale, int rows_per_sample, const void* add, float* U,
@@ -330,15 +323,13 @@ static int ring_launch(const void* A, const void* W, const float* bias, void* C,
     const int tiles_m = (M + bm - 1) / bm, tiles_n = (N + RBN - 1) / RBN;
     if ((long long)tiles_m * tiles_n > 0x7ffffff0LL) return GM3D_EUNSUPPORTED;
     const int total = tiles_m * tiles_n, grid = (total + 7) / 8 * 8;
-    const int depth = U ? 2 : RING_DEPTH[bm == 64 ? 0 : 1];
-    const size_t lds = (size_t)(depth + 2) * (bm + RBN) * 128;
-#define GM3D_RING(WMI, RES, DEPTH)                                                                                         \
-    launch_lds<gemm_tn_ring_kernel<WMI, RES, DEPTH>>(dim3(grid), dim3(256), lds, stream, (const bf16_t*)A, (const bf16_t*)W, bias, \
-                                                     (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total, res, rowscale,           \
-                                                     rows_per_sample, (const bf16_t*)add, U, stats, (bf16_t*)U16)
-    if (U) return bm == 64 ? GM3D_RING(1, true, 2) : GM3D_RING(2, true, 2);
-    if (bm == 64) return depth == 2 ? GM3D_RING(1, false, 2) : depth == 3 ? GM3D_RING(1, false, 3) : GM3D_RING(1, false, 4);
-    return depth == 2 ? GM3D_RING(2, false, 2) : GM3D_RING(2, false, 3);
+    const size_t lds = (size_t)(RING_DEPTH + 2) * (bm + RBN) * 128;
+#define GM3D_RING(WMI, RES)                                                                                                     \
+    launch_lds<gemm_tn_ring_kernel<WMI, RES, RING_DEPTH>>(dim3(grid), dim3(256), lds, stream, (const bf16_t*)A, (const bf16_t*)W, \
+                                                          bias, (bf16_t*)C, M, N, K, lda, ldw, ldc, tiles_n, total, res, rowscale, \
+                                                          rows_per_sample, (const bf16_t*)add, U, stats, (bf16_t*)U16)
+    if (U) return bm == 64 ? GM3D_RING(1, true) : GM3D_RING(2, true);
+    return bm == 64 ? GM3D_RING(1, false) : GM3D_RING(2, false);
 #undef GM3D_RING
 }
 

@@ -341,19 +341,12 @@ __global__ __launch_bounds__(64 * (NW + NL)) void gemm_tn_ws_kernel(const bf16_t
 
 }  // namespace gm3d
 
-// grid: one persistent workgroup per CU (a multiple of 8 and of tiles_n; never more than there are tiles)
-static int WS_WG_PER_CU = 2;      // measurement knob (gm3d_gemm_ws_set_occupancy): persistent workgroups per CU where LDS allows two
-
-extern "C" int gm3d_gemm_ws_set_occupancy(int wg_per_cu) {
-    WS_WG_PER_CU = wg_per_cu < 1 ? 1 : (wg_per_cu > 2 ? 2 : wg_per_cu);
-    return GM3D_OK;
-}
-
 using gm3d::ws_depth;
 
+// grid: persistent workgroups, two per CU where LDS allows two, else one (a multiple of 8 and of tiles_n; never more than there are tiles)
 static int ws_grid(int tiles_m, int tiles_n, size_t lds) {
     long long want = (long long)tiles_m * tiles_n;
-    const int cap = (WS_WG_PER_CU == 2 && 2 * lds <= 160 * 1024) ? 512 : 256;
+    const int cap = 2 * lds <= 160 * 1024 ? 512 : 256;
     int g = want < cap ? (int)want : cap;
     g = (g + 7) / 8 * 8;
     while (g % tiles_n) g += 8;

@@ -7,7 +7,7 @@ as driven by P/models_mae_learn_loss.py:914-917 and :984-990:
     for block in blocks:  x = block(x + pos)        # x += dp(attn(LN1(x)));  x += dp(mlp(LN2(x)))
     return LayerNorm(x)
 
-Per block the forward is 4 GEMMs (hipBLASLt via torch.mm on cached bf16 weights), the MFMA attention kernel and
+Per block the forward is 4 GEMMs (the MFMA kernels of csrc/gemm*.hip through gemm.mm, on cached bf16 weights), the MFMA attention kernel and
 3 row-wise HIP passes (gm3d_amd/csrc/rowops.hip): [residual + bias + DropPath + pos + LayerNorm] x2 and
 [bias + GELU]; the backward is 8 GEMMs, the attention backward and 3 row-wise passes that also produce every
 bias / gamma / beta gradient as fused column sums.  The residual stream is fp32, GEMM operands are bf16

@@ -6,7 +6,6 @@ import torch
 from ._capi import lib
 from .ops import _launch, _ptr, _stream
 
-import os
 
 ENABLED = True            # module attributes below: flipped by the equality tests and tools/, not environment switches
 FUSE_GELU = True          # fc1 + bias + GELU as one launch in the fused transformer stack
@@ -244,9 +243,6 @@ def linear_tn_dmaw(x, w, bias=None, out=None, bm=128, bn=256):
     return out
 
 
-N384_BIG = "ring128"      # N = 384 above 4096 rows.  "dma64x128" (two workgroups per CU) is 2-8 % faster launch by launch
-#                           (profiles/r03_gemm_kbench.txt) and 1.1 % SLOWER in the step (same-box A/B, gpurun_out/r3i: 8.08 vs 7.99 ms):
-#                           these launches run beside the other decoder's chain, which the second workgroup per CU displaces
 OWN_KT = (2, 4, 6, 8, 16, 18, 24)      # K / 64 values csrc/gemm.hip is unrolled for
 
 
@@ -260,7 +256,10 @@ def choose(M, N, K):
     if N == 384 and K in (384, 1024, 1152, 1536):       # three column tiles: 150 .. 192 workgroups for 256 CUs
         # the ring, one workgroup per CU, two K-stages in flight.  Neither 96-column tiles (every CU busy, fewer bytes per
         # workgroup) nor a deeper ring helps: the r03 table has both slower -- the chip-wide L2 -> LDS rate is what is exhausted
-        return "ring64" if M <= 4096 else N384_BIG
+        # above 4096 rows "dma64x128" (two workgroups per CU) is 2-8 % faster launch by launch (profiles/r03_gemm_kbench.txt) and
+        # 1.1 % SLOWER in the step (same-box A/B: 8.08 vs 7.99 ms): these launches run beside the other decoder's
+        # chain, which the second workgroup per CU displaces
+        return "ring64" if M <= 4096 else "ring128"
     if (N, K) == (1152, 384):
         return "ring128" if M <= 3200 else ("dma64x192" if M <= 4096 else "dma128x192") if USE_DMA else "own"
     if K == 384 and N % 192 == 0 and N > 384 and M < 32768:
@@ -428,10 +427,6 @@ def wgrad_supported(dy, x):
             and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and (dy.shape[0] == 1 or (dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0)))
 
 
-WGRAD_SPLITS_CAP = 0        # measurement knob: cap on the row splits of the WGRAD_SPLITS_CAP_NB-block stacks' products (0 = none)
-WGRAD_SPLITS_CAP_NB = 4
-
-
 FUSE_SLAB_SUM = False      # the sum over the row splits inside the NT launch (the last workgroup of a tile adds its slabs in slab order):
 #                            bit-identical, 17 launches fewer per step -- and 0.8-1.0 ms SLOWER (same-box A/B 8.32 / 8.59 vs 7.53 ms): the
 #                            agent-scope release fence every workgroup needs before it bumps the tile counter writes back its XCD's L2
@@ -463,26 +458,29 @@ from . import streams as _streams_mod  # noqa: E402
 _streams_mod.before_capture(lambda device: _nt_counter_slice(device, 0))   # the counters exist before any audited capture begins
 
 
-def wgrad_nt(dy, x, out=None, splits=None):
+def wgrad_nt(dy, x, out=None, splits=None, big_tiles=False):
     """out (nb,N,K) f32 = dy[b]^T @ x[b]  (dy (nb,R,N), x (nb,R,K) bf16) -- every weight gradient of a block stack in one launch,
     written into `out` (the parameters' slots of the flat gradient buffer) when given.  Long reductions over few output tiles
     are cut into `splits` row ranges whose fp32 partial products are added in slab order: inside the same launch for up to
-    FUSE_SLAB_SUM_MAX splits (gm3d_gemm_nt_bf16_sum), by gm3d_sum_few_rows beyond -- the same bits either way."""
+    FUSE_SLAB_SUM_MAX splits (gm3d_gemm_nt_bf16_sum), by gm3d_sum_few_rows beyond -- the same bits either way.
+    big_tiles: the 128 x 384-tile kernel (gm3d_gemm_nt_bf16_big, a measured-slower tested variant) with the caller's `splits`; its
+    slabs are always added by gm3d_sum_few_rows."""
     nb, R, N = dy.shape
     K = x.shape[2]
+    assert not big_tiles or splits is not None, "big_tiles: gm3d_gemm_nt_splits speaks for the 128 x 128 kernel, name the splits"
+    name = "gm3d_gemm_nt_bf16_big" if big_tiles else "gm3d_gemm_nt_bf16"
+    fn = getattr(lib, name)
     if splits is None:
         splits = lib.gm3d_gemm_nt_splits(nb, R, N, K)
-        if WGRAD_SPLITS_CAP and nb == WGRAD_SPLITS_CAP_NB and R <= 8192:
-            splits = min(splits, WGRAD_SPLITS_CAP)
     if out is None:
         out = torch.empty(nb, N, K, dtype=torch.float32, device=dy.device)
     assert out.dtype == torch.float32 and out.stride(2) == 1 and out.stride(1) >= K
     if splits == 1:
-        _launch("gm3d_gemm_nt_bf16", {"B": nb, "M": R, "N": N, "K": K}, lib.gm3d_gemm_nt_bf16, _ptr(dy), _ptr(x), _ptr(out), nb, R, N, K,
+        _launch(name, {"B": nb, "M": R, "N": N, "K": K}, fn, _ptr(dy), _ptr(x), _ptr(out), nb, R, N, K,
                 dy.stride(1), x.stride(1), out.stride(1), dy.stride(0), x.stride(0), out.stride(0), 1, 0, _stream())
         return out
     part = torch.empty(nb, splits, N, K, dtype=torch.float32, device=dy.device)
-    if (FUSE_SLAB_SUM and splits <= FUSE_SLAB_SUM_MAX and K % 4 == 0 and out.stride(1) % 4 == 0 and out.data_ptr() % 16 == 0
+    if (FUSE_SLAB_SUM and not big_tiles and splits <= FUSE_SLAB_SUM_MAX and K % 4 == 0 and out.stride(1) % 4 == 0 and out.data_ptr() % 16 == 0
             and (nb == 1 or out.stride(0) >= N * out.stride(1))):
         cnt = _nt_counter_slice(dy.device, nb * lib.gm3d_gemm_nt_tiles(N, K))
         if cnt is not None:
@@ -490,7 +488,7 @@ def wgrad_nt(dy, x, out=None, splits=None):
                     _ptr(out), _ptr(cnt), nb, R, N, K, dy.stride(1), x.stride(1), out.stride(1), dy.stride(0), x.stride(0), out.stride(0),
                     splits, _stream())
             return out
-    _launch("gm3d_gemm_nt_bf16", {"B": nb, "M": R, "N": N, "K": K}, lib.gm3d_gemm_nt_bf16, _ptr(dy), _ptr(x), _ptr(part), nb, R, N, K,
+    _launch(name, {"B": nb, "M": R, "N": N, "K": K}, fn, _ptr(dy), _ptr(x), _ptr(part), nb, R, N, K,
             dy.stride(1), x.stride(1), K, dy.stride(0), x.stride(0), splits * N * K, splits, N * K, _stream())
     if out.is_contiguous() or (out.stride(1) == K and out.stride(0) == N * K):
         _launch("gm3d_sum_few_rows", {"rows": nb * splits, "cols": N * K}, lib.gm3d_sum_few_rows, _ptr(part), nb, splits, N * K, _ptr(out),
@@ -506,11 +504,6 @@ MULTI_SPLITS_MAX = 2      # with MULTI_WGRAD: cap on the row splits of the 8192-
 MULTI_WGRAD = True        # the weight gradients of several stacks as ONE launch (+ one slab-sum launch): gm3d_gemm_nt_bf16_multi.  With each
 #                           problem's own splits: 22 launches fewer and no faster (7.64 vs 7.60 ms same-box); with the splits capped as above (fewer
 #                           slabs to write and add): 7.56 vs 7.65 ms, +1.1 %
-
-
-NT_TN_FASTEST = False     # measurement knob: tile order inside a (block, row-split) group of the one-launch weight gradients (csrc/gemm_nt.hip
-#                           gm3d_gemm_nt_set_order): PMC and step time equal either way (profiles/NEGATIVE_RESULTS.md, round 4)
-_nt_order_set = [False]
 
 
 def wgrad_multi_ok(dy, x, out):
@@ -562,9 +555,6 @@ def wgrad_nt_multi(reqs, splits=None, want_splits=False):
         outs.append(out)
         spl.append(s_)
         parts.append(torch.empty(nb, s_, N, K, dtype=torch.float32, device=dy.device) if s_ > 1 else None)
-    if _nt_order_set[0] != bool(NT_TN_FASTEST):
-        lib.gm3d_gemm_nt_set_order(int(bool(NT_TN_FASTEST)))
-        _nt_order_set[0] = bool(NT_TN_FASTEST)
     _launch("gm3d_gemm_nt_bf16_multi", {"count": n, "problems": [(r[0].shape[0], r[0].shape[1], r[0].shape[2], r[1].shape[2]) for r in reqs],
                                         "splits": list(spl)}, lib.gm3d_gemm_nt_bf16_multi, n,
             VP(*[_ptr(r[0]) for r in reqs]), VP(*[_ptr(r[1]) for r in reqs]), VP(*[_ptr(o) for o in outs]),

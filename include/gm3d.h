@@ -140,8 +140,6 @@ int gm3d_patch_chamfer_loss_bwd_full(const void *pred, long long pred_bstride, c
  * partial (gm3d_ln_plain_partial_rows(R), 2, C) f32: [.][0] = per-block sums of dh * xhat (dgamma), [.][1] = of dh (dbeta), to be
  * finished by gm3d_colsum_finish over 2*C columns. */
 int gm3d_ln_plain_partial_rows(int R);
-/* measurement knob: workgroup cap (= rows of partial sums) of the LayerNorm backward kernels for 8192 <= R < 32768 (default 512) */
-int gm3d_ln_set_grid_cap(int cap);
 int gm3d_ln_plain_fwd(const void *x, const float *gamma, const float *beta, float eps, void *h, float *mean, float *rstd, int R,
                       int C, int dtype, gm3d_stream_t stream);
 int gm3d_ln_plain_bwd(const void *dh, const void *x, const float *mean, const float *rstd, const float *gamma, void *dx,
@@ -432,9 +430,6 @@ int gm3d_gemm_tile_rows(int M);
  * last column tile: the 96-wide reconstruction head increase_dim_just_network_without_feature, models_mae_learn_loss.py:169-176). */
 int gm3d_gemm_tn_bf16_ring(const void *A, const void *W, const float *bias, void *C, int M, int N, int K, int lda, int ldw, int ldc,
                            int bm, gm3d_stream_t stream);
-/* Ring depth of gm3d_gemm_tn_bf16_ring: K-stages requested ahead of the one being multiplied (2 .. 4 for bm = 64, 2 .. 3 for
- * bm = 128; clamped).  Results do not depend on it.  Process-wide; set before capturing a graph. */
-int gm3d_gemm_ring_set_depth(int bm, int depth);
 /* The TALL products of the mini-PointNet (Encoder.first_conv.3 / second_conv.0 / second_conv.3 over the B*G*k = 262,144 point rows,
  * models_mae_learn_loss.py:876-882, and their input gradients; K <= 512) with the weights STATIONARY IN REGISTERS (csrc/gemm_ws.hip):
  * persistent workgroups, 32 output columns of W per wave for the whole K, A streamed once per column block through an LDS ring
@@ -469,8 +464,6 @@ int gm3d_gemm_tn_bf16_ws_bn_apply_g(const void *A, const void *W, const void *T,
 int gm3d_gemm_tn_bf16_ws_bn_stats_g(const void *A, const void *W, const void *T, void *C, float *partial, int M, int N, int K, int lda,
                                     int ldw, int ldt, int ldc, int group_rows, gm3d_stream_t stream);
 int gm3d_gemm_ws_stats_rows(int M, int N, int K);
-/* measurement knob: persistent workgroups per CU (1 or 2; two only where the LDS ring allows). Results do not depend on it. */
-int gm3d_gemm_ws_set_occupancy(int wg_per_cu);
 /* The ring kernel with 96-column tiles (N % 96 == 0): N = 384 -- attn.proj, mlp.fc2 and the input gradients of fc1 / qkv / proj of
  * the timm Block (Point-MAE_SA3D/models/Point_MAE.py:82-125) -- as four column tiles per row block instead of three: 200 / 256
  * workgroups instead of 150 / 192 for 256 CUs, each pulling fewer operand bytes from L2.  Bit-identical results.  bm = 64 or 128. */
@@ -528,14 +521,13 @@ int gm3d_gemm_nt_bf16(const void *dY, const void *X, float *out, int batch, int 
                       long long stride_y, long long stride_x, long long stride_o, int splits, long long stride_split,
                       gm3d_stream_t stream);
 int gm3d_gemm_nt_splits(int batch, int R, int N, int K);
-/* Tile shape of gm3d_gemm_nt_bf16 where (N, K) is a multiple of (128, 384) -- every weight of the transformer blocks: 0 (default) =
- * 128 x 128 output tiles everywhere, 1 = 128 x 384 tiles (512-thread workgroups, 1.5 x the flops per byte staged from L2, fragment reads
- * software-pipelined against the MFMAs; measured SLOWER on MI355X, kept as a tested variant).  Results are equal for equal row splits;
- * gm3d_gemm_nt_splits follows the setting.  Process-wide measurement knob; set before capturing a graph. */
-int gm3d_gemm_nt_set_big_tiles(int on);
-/* measurement knob of gm3d_gemm_nt_bf16_multi: tile order inside a (block, row-split) group -- 0 (default): the K-tiles of one dY column
- * block adjacent; 1: the N-tiles of one X column block adjacent */
-int gm3d_gemm_nt_set_order(int tn_fastest);
+/* gm3d_gemm_nt_bf16 on 128 x 384 output tiles (512-thread workgroups, 1.5 x the flops per byte staged from L2, fragment reads
+ * software-pipelined against the MFMAs; measured SLOWER on MI355X, kept as a tested variant that no product calls).  Same arguments;
+ * N % 128 == 0 and K % 384 == 0 -- every weight of the transformer blocks -- else GM3D_EUNSUPPORTED.  Results are equal to
+ * gm3d_gemm_nt_bf16's for equal row splits.  gm3d_gemm_nt_splits speaks for the 128 x 128 kernel only. */
+int gm3d_gemm_nt_bf16_big(const void *dY, const void *X, float *out, int batch, int R, int N, int K, int ldy, int ldx, int ldo,
+                          long long stride_y, long long stride_x, long long stride_o, int splits, long long stride_split,
+                          gm3d_stream_t stream);
 /* gm3d_gemm_nt_bf16 with the sum over the row splits INSIDE the launch (no gm3d_sum_few_rows pass): the workgroup that finishes a
  * tile's last slab adds that tile's slabs in slab order (bit-identical to the two-launch form, whatever the arrival order) and writes
  * out (batch, N, ldo; batch stride stride_o; ldo % 4 == 0).  part: (batch, splits, N, K) f32 scratch; counters: batch *
@@ -608,8 +600,6 @@ int gm3d_take_rows(const void *a, const long long *idx, void *out, int B, int S,
  * elem_bytes 2 or 4.  Gather into / scatter out of the compact order above, forward and backward (indices without repeats). */
 int gm3d_select_rows(const void *a, const int *idx, const void *alt, void *out, int B, int Ta, int T, int C, int elem_bytes,
                      gm3d_stream_t stream);
-/* measurement knob: 1 (default) = eight 32-row tiles per workgroup for HD <= 32 and T > 128, 0 = four everywhere */
-int gm3d_attention_masked_set_wide(int on);
 int gm3d_attention_masked_fwd(const void *qkv, const unsigned *mask, void *out, float *lse, int B, int T, int H, int HD, float scale,
                               int dtype, gm3d_stream_t stream);
 int gm3d_attention_masked_bwd(const void *qkv, const unsigned *mask, const void *out, const void *dout, const float *lse, void *dqkv,

@@ -118,6 +118,10 @@ def _add_ln_bwd(C, R=1):
     return _lib().gm3d_add_ln_bwd(ONE, None, ONE, ONE, ONE, ONE, None, 1, ONE, None, ONE, 2, R, C, 0, None)
 
 
+def _nt_big(N, K, batch=1):
+    return _lib().gm3d_gemm_nt_bf16_big(ONE, ONE, ONE, batch, 64, N, K, N, K, K, 64 * N, 64 * K, N * K, 1, 0, None)
+
+
 # (id, call(value, **kw), last accepted, first refused, empty-batch keyword that returns after the guard or None, extra kwargs)
 # The empty-batch keyword is given only where the guard runs before the entry point's early return for an empty batch.
 LIMITS = [
@@ -157,6 +161,9 @@ LIMITS = [
     ("ln_plain_bwd.C", _ln_plain_bwd, 512, 516, None, {}),                       # guard in rowops.hip (via gm3d_add_ln_bwd_acc)
     ("add_ln_fwd.C", _add_ln_fwd, 512, 516, "R", {}),                            # guard in rowops.hip
     ("add_ln_bwd.C", _add_ln_bwd, 512, 516, None, {}),                           # guard in rowops.hip
+    # whole 128 x 384 tiles only: the first refused value is a multiple of 8 (what gm3d_gemm_nt_bf16 takes) that is not a whole tile
+    ("gemm_nt_bf16_big.N", lambda n, batch=1: _nt_big(n, 384, batch), 128, 136, "batch", {}),      # guard in gemm_nt.hip (nt_launch)
+    ("gemm_nt_bf16_big.K", lambda k, batch=1: _nt_big(128, k, batch), 384, 392, "batch", {}),      # guard in gemm_nt.hip (nt_launch)
 ]
 
 # The lower ends and the alignment conditions of the same guards: refused values only.
@@ -171,6 +178,8 @@ REFUSED_ALSO = [
     ("ln_plain_fwd.C%4", lambda: _ln_plain_fwd(98)),                              # guard in rowops.hip
     ("ln_plain_fwd.C<4", lambda: _ln_plain_fwd(3)),                              # guard in rowops.hip (C = 3 is EUNSUPPORTED, not EINVAL)
     ("add_ln_bwd.C%4", lambda: _add_ln_bwd(98)),                                  # guard in rowops.hip
+    ("gemm_nt_bf16_big.K=128", lambda: _nt_big(128, 128)),                        # guard in gemm_nt.hip: a 128 x 128 tile is not a big one
+    ("gemm_nt_bf16_big.N%8", lambda: _nt_big(132, 384)),                          # guard in gemm_nt.hip (shared with gm3d_gemm_nt_bf16)
 ]
 
 

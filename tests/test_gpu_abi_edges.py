@@ -455,3 +455,21 @@ def test_cls_tail_vote_edges(V, cls_dim):
         assert rel(mean, want.sum(0) / V) <= 1e-5
         assert torch.equal(pred, mean.argmax(-1))
         assert int(correct) == int((pred == labels).sum())
+
+
+# ------------------------------------------------------------------ weight gradients on 128 x 384 tiles: one whole tile, one stage per split
+@pytest.mark.parametrize("nb,R,N,K,splits", [(1, 32, 128, 384, 1), (2, 128, 128, 384, 4), (1, 64, 256, 768, 2), (3, 4096, 128, 384, 1)])
+def test_gemm_nt_big_tiles_smallest_shapes(nb, R, N, K, splits):
+    """gm3d_gemm_nt_bf16_big at the smallest (N, K) its guard accepts -- one 128 x 384 tile -- and with a single 32-row stage per row
+    split, through the raw entry point into a guarded slab buffer: the slab sum against an fp32 torch.bmm of the same bf16 operands at
+    the bar of test_gemm_nt_weight_gradient (fp32 accumulation error only)."""
+    from gm3d_amd.ops import _ptr
+    g = torch.Generator(device="cuda").manual_seed(R + N + K + splits)
+    dy = torch.randn(nb, R, N, device="cuda", generator=g).bfloat16()
+    x = torch.randn(nb, R, K, device="cuda", generator=g).bfloat16()
+    part = Guarded((nb, splits, N, K), torch.float32, NAN)
+    _ok(_lib().gm3d_gemm_nt_bf16_big(_ptr(dy), _ptr(x), _ptr(part.t), nb, R, N, K, N, K, K, R * N, R * K, splits * N * K, splits, N * K,
+                                     None), "gm3d_gemm_nt_bf16_big")
+    got = part.check("slabs").sum(1)
+    want = torch.bmm(dy.float().transpose(1, 2), x.float())
+    assert float((got - want).abs().max()) <= 2e-5 * float(want.abs().max()) * max(1.0, (R / 4096) ** 0.5)

@@ -19,7 +19,6 @@ ap.add_argument("--points", type=int, default=8192)
 ap.add_argument("--fp32", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda")
-E.enable_tuned_gemms()
 torch.manual_seed(0)
 cfg = dict(trans_dim=384, depth=12, drop_path_rate=0.1, cls_dim=40, num_heads=6, group_size=32, num_group=64, encoder_dims=384)
 model = PointTransformer(cfg).to(dev).train()

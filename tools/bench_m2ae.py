@@ -18,7 +18,6 @@ ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--staged", action="store_true", help="A/B: training graph + the next batch's grouping graph on a second stream")
 ap.add_argument("--set", action="append", default=[], metavar="mod.ATTR=value",
                 help="flip a module switch of gm3d_amd for a same-box A/B (e.g. --set gemm.WS_BN=False --set point_m2ae.VISIBLE_FIRST=False)")
-ap.add_argument("--narrow-attn", action="store_true", help="A/B: four tiles per workgroup in the masked attention kernels (the round-3 form)")
 ap.add_argument("--epoch", action="store_true", help="time engine_pretrain_m2ae.train_one_epoch (in-memory loader of --steps batches)")
 ap.add_argument("--rehearse-gloo", action="store_true", help="--epoch with two ranks on GPU 0 over gloo (a rehearsal, not a measurement)")
 a = ap.parse_args()
@@ -49,14 +48,7 @@ import importlib
 for item in a.set:
     name, val = item.split("=")
     mod, attr = name.rsplit(".", 1)
-    if mod == "capi":          # --set capi.gm3d_gemm_ws_set_tm2=1: a process-wide knob of the C ABI
-        from gm3d_amd._capi import lib as _l
-        assert getattr(_l, attr)(int(eval(val))) == 0
-        continue
     setattr(importlib.import_module("gm3d_amd." + mod), attr, eval(val))
-if a.narrow_attn:
-    from gm3d_amd._capi import lib as _lib
-    _lib.gm3d_attention_masked_set_wide(0)
 
 
 def epoch_bench():

@@ -55,12 +55,10 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
 from gm3d_amd import engine_finetune as EF  # noqa: E402
-from gm3d_amd import engine_pretrain as E  # noqa: E402
 from gm3d_amd import point_m2ae_cls as C  # noqa: E402
 from bench import make_clouds  # noqa: E402
 
 dev = torch.device("cuda")
-E.enable_tuned_gemms()
 torch.manual_seed(0)
 cfg = dict(NAME="Point_M2AE_ModelNet40", group_sizes=[16, 8, 8], num_groups=[512, 256, 64], encoder_depths=[5, 5, 5],
            encoder_dims=[96, 192, 384], local_radius=[0.32, 0.64, 1.28], drop_path_rate=0.1, num_heads=6, cls_dim=40)

@@ -14,7 +14,7 @@ import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from gm3d_amd import engine_finetune as EF, engine_pretrain as E, ops
+from gm3d_amd import engine_finetune as EF, ops
 from gm3d_amd import point_m2ae_cls as C
 from bench import make_clouds
 
@@ -29,7 +29,6 @@ ap.add_argument("--forms", default="reference,batched,graphed")
 ap.add_argument("--no-launch-count", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda")
-E.enable_tuned_gemms()
 torch.manual_seed(0)
 cfg = dict(NAME="Point_M2AE_ModelNet40", group_sizes=[16, 8, 8], num_groups=[512, 256, 64], encoder_depths=[5, 5, 5],
            encoder_dims=[96, 192, 384], local_radius=[0.32, 0.64, 1.28], drop_path_rate=0.1, num_heads=6, cls_dim=40)

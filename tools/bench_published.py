@@ -15,7 +15,6 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 a = ap.parse_args()
 dev = torch.device("cuda")
-E.enable_tuned_gemms()
 torch.manual_seed(0)
 model = V.mae_vit_base_patch16_dec512d8b().to(dev).train()
 teacher = Point_MAE({"group_size": 32, "num_group": 64, "loss": "cdl2",

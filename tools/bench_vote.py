@@ -11,7 +11,7 @@ import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from gm3d_amd import engine_finetune as EF, engine_pretrain as E, ops
+from gm3d_amd import engine_finetune as EF, ops
 from gm3d_amd.point_transformer import PointTransformer
 from bench import make_clouds
 
@@ -23,7 +23,6 @@ ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--points", type=int, default=8192)
 a = ap.parse_args()
 dev = torch.device("cuda")
-E.enable_tuned_gemms()
 torch.manual_seed(0)
 cfg = dict(trans_dim=384, depth=12, drop_path_rate=0.1, cls_dim=40, num_heads=6, group_size=32, num_group=64, encoder_dims=384)
 model = PointTransformer(cfg).to(dev).eval()

@@ -8,13 +8,6 @@ cut = args.index("--") if "--" in args else len(args)
 for item in args[:cut]:
     name, val = item.split("=")
     mod, attr = name.rsplit(".", 1)
-    if mod == "capi":          # capi.gm3d_ln_set_grid_cap=1024 -> call a process-wide knob of the C ABI
-        import torch
-        torch.cuda.init()           # (the HIP runtime first, as in bench.py: the library's first launch otherwise reports a stale error)
-        torch.zeros(1, device="cuda")
-        from gm3d_amd._capi import lib
-        assert getattr(lib, attr)(int(eval(val))) == 0
-        continue
     parts, obj = mod.split("."), None          # engine_pretrain.SegmentedDDPStep._reduce=... : module first, then attributes of it
     for cutp in range(len(parts), 0, -1):
         try:

@@ -1,5 +1,6 @@
-"""Ring depth of csrc/gemm_ring.hip in a DEPENDENT chain (operands just written by the previous kernel, i.e. not L2-hot as in
-tools/gemm_kbench.py): fc1(+GELU, LDS-DMA kernel) -> fc2 (ring kernel) x 12, replayed as one graph, for ring depths 2 / 3 / 4.
+"""The ring kernel of csrc/gemm_ring.hip in a DEPENDENT chain (operands just written by the previous kernel, i.e. not L2-hot as in
+tools/gemm_kbench.py): fc1(+GELU, LDS-DMA kernel) -> fc2 (ring kernel) x 12, replayed as one graph, for both tile heights.  (The
+ring-depth sweep this tool once ran is recorded in profiles/; to measure another depth, patch RING_DEPTH in a scratch copy of the kernel.)
     python tools/chain_depth.py [M]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,18 +40,15 @@ def timed(fn, n=20):
 
 
 for bm in (64, 128):
-    for depth in (2, 3, 4):
-        gemm.lib.gm3d_gemm_ring_set_depth(bm, depth)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            chain(bm)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=s):
-                keep = chain(bm)
-        torch.cuda.current_stream().wait_stream(s)
-        for _ in range(3):
-            g.replay()
-        print("M=%d  ring bm=%d depth=%d   %.1f us per block (fc1 + fc2 + proj)" % (M, bm, depth, timed(g.replay) / blocks), flush=True)
-    gemm.lib.gm3d_gemm_ring_set_depth(bm, 2)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        chain(bm)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            keep = chain(bm)
+    torch.cuda.current_stream().wait_stream(s)
+    for _ in range(3):
+        g.replay()
+    print("M=%d  ring bm=%d   %.1f us per block (fc1 + fc2 + proj)" % (M, bm, timed(g.replay) / blocks), flush=True)

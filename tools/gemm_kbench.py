@@ -1,11 +1,10 @@
-"""Own MFMA GEMM vs hipBLASLt (torch.mm, TunableOp table loaded) on the step's shapes; captured trains of launches, HIP events.
+"""Own MFMA GEMM vs hipBLASLt (torch.mm, the library's default heuristic) on the step's shapes; captured trains of launches, HIP events.
 python tools/gemm_kbench.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from gm3d_amd import gemm, engine_pretrain as E
+from gm3d_amd import gemm
 
-E.enable_tuned_gemms()
 dev = torch.device("cuda")
 SHAPES = [(4096, 384, 1152), (4096, 384, 384), (4096, 384, 1536), (4096, 1536, 384), (4096, 1152, 384), (8192, 384, 1152), (8192, 384, 384), (8192, 384, 1536), (8192, 1536, 384), (8192, 1152, 384),
           (3200, 384, 1152), (3200, 384, 384), (3200, 384, 1536), (3200, 1536, 384), (3200, 1152, 384),
@@ -50,19 +49,14 @@ if __name__ == "__main__":
         if K // 64 in gemm.OWN_KT:
             res["own"] = train(lambda x, w, o: gemm.linear_tn(x, w, out=o), sets)
         for bm in (64, 128):
-            for depth in ((2, 3, 4) if bm == 64 else (2, 3)):
-                gemm.lib.gm3d_gemm_ring_set_depth(bm, depth)
-                res["ring%d%s" % (bm, "" if depth == 2 else "d%d" % depth)] = train(lambda x, w, o: gemm.linear_tn_ring(x, w, out=o, bm=bm), sets)
-            gemm.lib.gm3d_gemm_ring_set_depth(bm, 2)
+            res["ring%d" % bm] = train(lambda x, w, o: gemm.linear_tn_ring(x, w, out=o, bm=bm), sets)
             if N % 96 == 0:
                 res["r96_%d" % bm] = train(lambda x, w, o: gemm.linear_tn_ring96(x, w, out=o, bm=bm), sets)
             for bn in (128, 192, 256):
                 if N % bn == 0:
                     res["dma%dx%d" % (bm, bn)] = train(lambda x, w, o: gemm.linear_tn_dmaw(x, w, out=o, bm=bm, bn=bn), sets)
         if M >= 32768 and gemm.lib.gm3d_gemm_ws_supported(N, K, 0):
-            for occ in (1, 2):
-                gemm.lib.gm3d_gemm_ws_set_occupancy(occ)
-                res["ws%d" % occ] = train(lambda x, w, o: gemm.linear_tn_ws(x, w, out=o), sets)
+            res["ws"] = train(lambda x, w, o: gemm.linear_tn_ws(x, w, out=o), sets)
         best = min((v, k) for k, v in res.items() if k != "lib")
         hbm = 2.0 * (M * K + M * N + N * K) / 1e6          # MB: A once, C once, W once
         print("M=%6d K=%4d N=%4d  lib %7.1f us | " % (M, K, N, res["lib"]) + "  ".join("%s %.1f" % (k, v) for k, v in res.items() if k != "lib")

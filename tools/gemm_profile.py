@@ -10,7 +10,6 @@ from bench import make_clouds
 
 B = int(os.environ.get("B", 128))
 dev = torch.device("cuda")
-E.enable_tuned_gemms()
 torch.manual_seed(0)
 model = M.mae_vit_base_patch16_dec512d8b().to(dev).train()
 ema = E.ModelEma(model, 0.9999)

@@ -5,7 +5,6 @@ import torch
 from types import SimpleNamespace
 from gm3d_amd import engine_pretrain as E, models_mae_learn_loss as M
 from bench import make_clouds
-E.enable_tuned_gemms()
 dev = torch.device("cuda")
 args = SimpleNamespace(mask_ratio=0.6, epochs=400, relative=True, bf16=True, accum_iter=1, lr=1e-3, min_lr=0.0, warmup_epochs=40)
 pool = [make_clouds(128, 1024, 10 + i, dev) for i in range(3)]

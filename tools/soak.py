@@ -12,7 +12,6 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=600)
 ap.add_argument("--batch", type=int, default=128)
 a = ap.parse_args()
-E.enable_tuned_gemms()
 torch.manual_seed(0)
 dev = torch.device("cuda")
 model = M.mae_vit_base_patch16_dec512d8b().to(dev).train()
