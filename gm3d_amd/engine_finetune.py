@@ -164,12 +164,7 @@ class GraphedFinetuneStep:
             self.pts.copy_(sample_points(self.points, npoints, subset=self.subset))
             self.sstream = torch.cuda.Stream()
             self._ready, self._staged = torch.cuda.Event(), False
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup_iters):
-                self._body()
-        torch.cuda.current_stream().wait_stream(side)
+        streams.warm_up(self._body, warmup_iters)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with streams.capture(self.graph):
@@ -439,11 +434,7 @@ class GraphedVoteEval:
         was = self.model.training
         self.model.eval()
         try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._body(torch.zeros(1, dtype=torch.long, device=self.points.device))    # warm-up, its own counter
-            torch.cuda.current_stream().wait_stream(side)
+            streams.warm_up(lambda: self._body(torch.zeros(1, dtype=torch.long, device=self.points.device)), 1)    # its own counter
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with streams.capture(self.graph):

@@ -21,6 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import streams
+from .segmented import SegmentedStep, _broadcast_tensors, broadcast_buffers, broadcast_state, step_update  # noqa: F401 (part of this module's interface)
 
 # --------------------------------------------------------------------------- augmentation
 class PointcloudScaleAndTranslate(object):
@@ -226,7 +227,7 @@ class GradSync:
         self._pending = [len(ps) for _, ps in self.buckets]
         self._works = []
         self._launched = [False] * len(self.buckets)
-        # (one rank: SUM, see SegmentedDDPStep.__init__)
+        # (one rank: SUM, see segmented.SegmentedStep.__init__)
         self._avg = dist.is_initialized() and dist.get_backend(process_group) == "nccl" and self.world > 1
         self.overlap = True   # False: hooks stay silent and finish() issues every bucket (used around captured graphs)
         for p in self.params:
@@ -258,7 +259,7 @@ class GradSync:
         self._flat = G
         self._pending = [len(ps) for _, ps in self.buckets]
         self._works, self._launched = [], [False] * len(self.buckets)
-        # (one rank: SUM, see SegmentedDDPStep.__init__)
+        # (one rank: SUM, see segmented.SegmentedStep.__init__)
         self._avg = dist.is_initialized() and dist.get_backend(process_group) == "nccl" and self.world > 1
         self.overlap = False          # gradients reach the flat buffer by one gather at the end of backward
         return self
@@ -317,66 +318,6 @@ class GradSync:
         # ready for the next step whether or not the caller goes through zero_grad() (the flat path zeroes through the
         # optimizer, and a replayed graph calls nothing at all): every finish() issues one collective per bucket
         self.reset()
-
-
-def _broadcast_tensors(tensors, src=0, group=None):
-    """Coalesced broadcast: one collective per dtype (pack, broadcast, unpack)."""
-    by_dtype = {}
-    for t in tensors:
-        by_dtype.setdefault(t.dtype, []).append(t)
-    with torch.no_grad():
-        for ts in by_dtype.values():
-            flat = torch.cat([t.reshape(-1) for t in ts])
-            dist.broadcast(flat, src=src, group=group)
-            off = 0
-            for t in ts:
-                t.copy_(flat[off:off + t.numel()].view_as(t))
-                off += t.numel()
-
-
-def broadcast_state(model=None, model_ema=None, optimizer=None, src=0, group=None):
-    """What the DDP constructor does at P/main_pretrain_multi_gpu.py:309-311, extended to everything a rank keeps: rank `src`'s
-    student parameters and buffers (integer counters included), EMA teacher and -- for FlatAdamWEma -- the flat master / moment
-    buffers and the step counter overwrite the other ranks'; the bf16 GEMM shadows are re-derived.  No-op without a group of >1."""
-    if not dist.is_initialized() or dist.get_world_size(group) == 1:
-        return
-    ts = []
-    flat = optimizer is not None and hasattr(optimizer, "flat_grad_views")
-    if flat:
-        ts += [optimizer.P, optimizer.M, optimizer.V, optimizer.step_dev]
-        if optimizer.E is not None:
-            ts.append(optimizer.E)
-    seen = {t.data_ptr() for t in ts}
-    lo, hi = (optimizer.P.data_ptr(), optimizer.P.data_ptr() + optimizer.P.numel() * 4) if flat else (0, 0)
-    elo, ehi = (optimizer.E.data_ptr(), optimizer.E.data_ptr() + optimizer.E.numel() * 4) if flat and optimizer.E is not None else (0, 0)
-    for mod in (model.module if hasattr(model, "module") else model, getattr(model_ema, "ema", model_ema)):
-        if mod is None:
-            continue
-        for t in list(mod.parameters()) + list(mod.buffers()):
-            a = t.data_ptr()
-            if a in seen or lo <= a < hi or elo <= a < ehi:       # views of the flat buffers travel with them
-                continue
-            seen.add(a)
-            ts.append(t.data)
-    _broadcast_tensors(ts, src=src, group=group)
-    if flat:
-        optimizer.sync_shadows()
-
-
-def broadcast_buffers(model, src=0, group=None):
-    """DDP's default broadcast_buffers=True: rank 0's BatchNorm running statistics overwrite the other
-    ranks' before the forward pass; one coalesced collective (3 launches: pack, broadcast, unpack)."""
-    bufs = [b for b in model.buffers() if b.dtype.is_floating_point]
-    if not bufs or not dist.is_initialized() or dist.get_world_size(group) == 1:
-        return
-    flat = torch.cat([b.reshape(-1) for b in bufs])
-    dist.broadcast(flat, src=src, group=group)
-    views, off = [], 0
-    for b in bufs:
-        views.append(flat[off:off + b.numel()].view_as(b))
-        off += b.numel()
-    with torch.no_grad():
-        torch._foreach_copy_(bufs, views)
 
 
 def shard_for_rank(n_items, rank, world, epoch=0, seed=0, shuffle=True):
@@ -525,19 +466,6 @@ def step_forward_backward(model, model_ema, samples, epoch, args, grad_sync=None
             "teacher_loss_pred": outs_ema["loss_pred"]}
 
 
-def step_update(model, model_ema, optimizer, clip_grad=5.0):
-    """Second half (P/util/misc.py:262-266 + P/engine_pretrain.py:208-212): clip -> AdamW -> EMA."""
-    raw = model.module if hasattr(model, "module") else model
-    if hasattr(optimizer, "flat_grad_views"):      # FlatAdamWEma: clip + AdamW + EMA(params) + bf16 shadows, one pass
-        grad_norm = optimizer.step()
-        model_ema.update(raw)                      # BatchNorm buffers only
-        return grad_norm
-    grad_norm = torch.nn.utils.clip_grad_norm_(raw.parameters(), clip_grad, foreach=True)
-    optimizer.step()
-    model_ema.update(raw)
-    return grad_norm
-
-
 def pretrain_step(model, model_ema, optimizer, samples, epoch, args, grad_sync=None, mask_noise=None,
                   augment=True, aug_draws=None, clip_grad=5.0, micro_step=None):
     """One iteration of P/engine_pretrain.py:77-212.  `samples` (B,N,3) f32 on the GPU (modified in
@@ -619,12 +547,7 @@ class GraphedPretrainStep:
             return out
 
         if warmup_iters:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup_iters):
-                    whole(self.static_in.clone())
-            torch.cuda.current_stream().wait_stream(side)
+            streams.warm_up(lambda: whole(self.static_in.clone()), warmup_iters)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         # with a process group alive its watchdog thread polls events; only the capturing thread's calls may abort a capture
@@ -673,7 +596,7 @@ class GraphedPretrainStep:
         return self.out
 
 
-class SegmentedDDPStep:
+class SegmentedDDPStep(SegmentedStep):
     """Data-parallel pretrain step with the gradient all-reduce hidden behind backward, as FOUR hipGraphs with eager RCCL
     collectives between them (no collective is captured):
 
@@ -686,133 +609,93 @@ class SegmentedDDPStep:
     The backward is cut with torch.autograd.grad at the tensors where the segments meet (x_vis / pos_full: encoder output and
     decoder positions; tokens / pos_all: embed outputs), so the sum of the three partial backwards is exactly the single
     backward -- tests/test_gpu_graph.py checks it against the un-segmented step.  Needs FlatAdamWEma built with
-    segment_of=ddp_segment: each segment's weight gradients are one contiguous range of the flat buffer.
+    segment_of=ddp_segment.
     While graph 2 runs, RCCL's stream reduces segment 0 (57 MB); while graph 3 runs, segment 1 (85 MB); only segment 2's
     ~5 MB collective is exposed.
     Construction broadcasts rank 0's parameters, optimizer state, EMA teacher and buffers (DDP's constructor does the same for
     the model; the reference seeds every rank differently, P/main_pretrain_multi_gpu.py:175-176).
-    args.accum_iter > 1: the segments' gradients are summed over the window in a second flat buffer and the three collectives
-    run once, on the sums, after the window's last backward (no overlap in that mode)."""
+    The group, the collectives, the capture chain and the replay loop (gradient accumulation included) are
+    segmented.SegmentedStep's; this class is the three cuts."""
+
+    NSEG = 3
 
     def __init__(self, model, model_ema, optimizer, args, example, epoch, warmup_iters=3, augment=True, inject_mask_noise=False,
                  process_group=None, use_graphs=True, broadcast=True):
         assert getattr(optimizer, "segment_ranges", None) is not None, "build the optimizer with segment_of=ddp_segment"
-        self.model, self.ema, self.opt, self.args, self.epoch = model, model_ema, optimizer, args, epoch
-        self.raw = model.module if hasattr(model, "module") else model
-        self.group, self.augment = process_group, augment
-        self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
-        # RCCL averages inside its ring kernel (ReduceOp.AVG).  A group of ONE rank keeps SUM: AVG there runs RCCL's one-rank
-        # pre-multiply kernel over the whole range (71 us per collective measured, 0.21 ms per step: tools/seg_timeline.py), which
-        # no N > 1 run executes -- a one-rank rehearsal of the layout should not be charged for it.
-        self._avg = dist.is_initialized() and dist.get_backend(process_group) == "nccl" and self.world > 1
-        self.accum = getattr(args, "accum_iter", 1)
-        if broadcast:
-            broadcast_state(self.raw, model_ema, optimizer, group=process_group)
-        L = self.raw.num_group
+        SegmentedStep.__init__(self, model, model_ema, optimizer, args, epoch, process_group, broadcast)
+        self.augment = augment
         self.static_in = example.clone()
-        self.static_noise = torch.rand(example.shape[0], L, device=example.device) if inject_mask_noise else None
-        views = dict((id(p), g) for p, g in optimizer.flat_grad_views())
-        self.seg_params = {sg: [p for p in ps] for sg, ps in optimizer.segment_params.items()}
-        self.seg_views = {sg: [views[id(p)] for p in ps] for sg, ps in self.seg_params.items()}
+        self.static_noise = torch.rand(example.shape[0], self.raw.num_group, device=example.device) if inject_mask_noise else None
         self.use_graphs = use_graphs
-        self.graphs = None
         if use_graphs:
             if warmup_iters:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    for _ in range(warmup_iters):
-                        self._eager(self.static_in.clone())
-                torch.cuda.current_stream().wait_stream(side)
+                streams.warm_up(lambda: self._eager(self.static_in.clone()), warmup_iters)
             torch.cuda.synchronize()
-            import os
-            mode = "thread_local" if dist.is_initialized() else "global"
-            self.graphs = [torch.cuda.CUDAGraph() for _ in range(4)]
-            with streams.capture(self.graphs[0], capture_error_mode=mode):
-                self.out = self._phase1(self.static_in)
-            for k, phase in ((1, self._phase2), (2, self._phase3)):
-                with streams.capture(self.graphs[k], pool=self.graphs[0].pool(), capture_error_mode=mode):
-                    phase()
-            with streams.capture(self.graphs[3], pool=self.graphs[0].pool(), capture_error_mode=mode):
-                self.opt.mark_grads_filled()
-                self.out["grad_norm"] = step_update(model, model_ema, optimizer)
+            self._capture(self.static_in)
 
-    # ---- the three backward segments --------------------------------------------------------------------------------
-    def _store(self, seg, grads):
-        """gradients of one segment -> their slots of the flat buffer (ONE multi-tensor copy; unused parameters: zeros)."""
-        views, have, zero = self.seg_views[seg], [], []
-        for v, g in zip(views, grads):
-            if g is not None and g.data_ptr() == v.data_ptr():
-                continue                      # written into its slot by the backward node itself (fused._wgrad_batched)
-            (have if g is not None else zero).append((v, g))
-        if have:
-            torch._foreach_copy_([v for v, _ in have], [g for _, g in have])
-        if zero:
-            torch._foreach_zero_([v for v, _ in zero])
-
-    def _phase1(self, samples):
-        raw, teacher, args, epoch = self.raw, self.ema.ema, self.args, self.epoch
-        self.opt.zero_grad(set_to_none=True)       # no stale p.grad may be gathered over the segment gradients by step()
-        L = raw.num_group
-        len_keep = int(L * (1 - args.mask_ratio))
-        if self.augment:
-            samples = train_transforms(samples)
-        bf16 = getattr(args, "bf16", False)
-        if bf16:
-            from .fused import weight_cache
-            weight_cache.pin(raw)
-            weight_cache.pin(teacher)
-            weight_cache.refresh()
-        amp = torch.autocast("cuda", dtype=torch.bfloat16) if bf16 else nullcontext()
-        B = samples.shape[0]
-        visible_mask = _all_false(B, L, samples.device)      # read only
-        with amp:
-            with torch.no_grad():
-                group = teacher.group_divider(samples)
-                all_ids = (_arange_ids(B, L, samples.device), _arange_ids(B, 0, samples.device))
-                outs_ema = teacher(samples, mask=visible_mask, num_visible=L, group=group, need_pix_pred=False, ids=all_ids)
-                mask, vis_ids, mask_ids, bool_masked_pos = teacher.generate_mask_ids(
-                    outs_ema["loss_pred"], mask_ratio=args.mask_ratio, guide=True, epoch=epoch, total_epoch=args.epochs, noise=self.static_noise,
-                    want_bool=True)
-            from . import models_mae_learn_loss as MM
-            vis_only = MM.VISIBLE_EMBED and raw.encoder.fused(group[0]) and vis_ids.shape[1] < L
-            # segment 2 | segment 1 boundary: the encoder sees detached leaves (the visible tokens only, when the embed can stop there)
-            tokens = raw.encoder(group[0], vis_ids=vis_ids if vis_only else None)
-            pos_all = raw.embed_pos(group[1])
-            tokens_d, pos_all_d = tokens.detach().requires_grad_(True), pos_all.detach().requires_grad_(True)
-            outs = self.model(samples, mask=bool_masked_pos, num_visible=len_keep, group=group, tokens=tokens_d, pos_all=pos_all_d,
-                              ids=(vis_ids, mask_ids), cut=True, tokens_visible=vis_only)
-            M = outs["mask_num"]
-            loss_outs = raw.forward_loss(outs["pix_pred"][:, -M:], outs["neighborhood"], outs["mask"], mask_ids=mask_ids,
-                                         full_pred=outs["pix_pred"])
-            loss_mse, loss_chfr = loss_outs["MSE_mean"], loss_outs["Chamfer_mean"]
-            loss = loss_chfr if loss_outs.get("MSE_zero") else 13.889 * loss_mse + 1.0 * loss_chfr
-            loss_learn = raw.forward_learning_loss(outs["loss_pred"][:, -M:], bool_masked_pos, loss_outs["matrix"].detach(),
-                                                   relative=args.relative, full_pred=outs["loss_pred"])
-        accum = getattr(args, "accum_iter", 1)
-        x_vis_d, pos_full_d = outs["features"], outs["pos_full"]   # segment 1 | segment 0 boundary (detached leaves)
-        p0 = self.seg_params[0]
-        seed = _const_scalar(loss.device, 1.0 / accum)             # two roots seeded with 1 / accum: no sum, division, ones_like
-        g = torch.autograd.grad([loss, loss_learn], p0 + [x_vis_d, pos_full_d], grad_outputs=[seed, seed], allow_unused=True)
-        self._store(0, g[:len(p0)])
-        self._cut1 = outs["cut"] + (g[len(p0)], g[len(p0) + 1])
-        self._cut2 = (tokens, pos_all, tokens_d, pos_all_d)
-        return {"loss": loss.detach(), "loss_learn": loss_learn.detach(), "loss_chfr": loss_chfr.detach(),
-                "loss_mse": loss_mse.detach(), "mask": bool_masked_pos, "matrix": loss_outs["matrix"].detach(),
-                "teacher_loss_pred": outs_ema["loss_pred"]}
-
-    def _phase2(self):
-        x_vis, pos_full, gx, gp = self._cut1
-        tokens_d, pos_all_d = self._cut2[2], self._cut2[3]
-        p1 = self.seg_params[1]
-        outs = [t for t, gt in ((x_vis, gx), (pos_full, gp)) if gt is not None]
-        gouts = [gt for gt in (gx, gp) if gt is not None]
-        g = torch.autograd.grad(outs, p1 + [tokens_d, pos_all_d], grad_outputs=gouts, allow_unused=True)   # (no fused.async_wgrad
-        # region around a segment: measured 7.98 vs 7.87 ms with one around this one, profiles/NEGATIVE_RESULTS.md round 4)
-        self._store(1, g[:len(p1)])
-        self._cut3 = (g[len(p1)], g[len(p1) + 1])
-
-    def _phase3(self):
+    def _segment(self, k, samples=None):
+        """0: forward + backward of losses, heads and both decoders; 1: the encoder stack; 2: token embed + positional embed."""
+        if k == 0:
+            raw, teacher, args, epoch = self.raw, self.ema.ema, self.args, self.epoch
+            self.opt.zero_grad(set_to_none=True)       # no stale p.grad may be gathered over the segment gradients by step()
+            L = raw.num_group
+            len_keep = int(L * (1 - args.mask_ratio))
+            if self.augment:
+                samples = train_transforms(samples)
+            bf16 = getattr(args, "bf16", False)
+            if bf16:
+                from .fused import weight_cache
+                weight_cache.pin(raw)
+                weight_cache.pin(teacher)
+                weight_cache.refresh()
+            amp = torch.autocast("cuda", dtype=torch.bfloat16) if bf16 else nullcontext()
+            B = samples.shape[0]
+            visible_mask = _all_false(B, L, samples.device)      # read only
+            with amp:
+                with torch.no_grad():
+                    group = teacher.group_divider(samples)
+                    all_ids = (_arange_ids(B, L, samples.device), _arange_ids(B, 0, samples.device))
+                    outs_ema = teacher(samples, mask=visible_mask, num_visible=L, group=group, need_pix_pred=False, ids=all_ids)
+                    mask, vis_ids, mask_ids, bool_masked_pos = teacher.generate_mask_ids(
+                        outs_ema["loss_pred"], mask_ratio=args.mask_ratio, guide=True, epoch=epoch, total_epoch=args.epochs, noise=self.static_noise,
+                        want_bool=True)
+                from . import models_mae_learn_loss as MM
+                vis_only = MM.VISIBLE_EMBED and raw.encoder.fused(group[0]) and vis_ids.shape[1] < L
+                # segment 2 | segment 1 boundary: the encoder sees detached leaves (the visible tokens only, when the embed can stop there)
+                tokens = raw.encoder(group[0], vis_ids=vis_ids if vis_only else None)
+                pos_all = raw.embed_pos(group[1])
+                tokens_d, pos_all_d = tokens.detach().requires_grad_(True), pos_all.detach().requires_grad_(True)
+                outs = self.model(samples, mask=bool_masked_pos, num_visible=len_keep, group=group, tokens=tokens_d, pos_all=pos_all_d,
+                                  ids=(vis_ids, mask_ids), cut=True, tokens_visible=vis_only)
+                M = outs["mask_num"]
+                loss_outs = raw.forward_loss(outs["pix_pred"][:, -M:], outs["neighborhood"], outs["mask"], mask_ids=mask_ids,
+                                             full_pred=outs["pix_pred"])
+                loss_mse, loss_chfr = loss_outs["MSE_mean"], loss_outs["Chamfer_mean"]
+                loss = loss_chfr if loss_outs.get("MSE_zero") else 13.889 * loss_mse + 1.0 * loss_chfr
+                loss_learn = raw.forward_learning_loss(outs["loss_pred"][:, -M:], bool_masked_pos, loss_outs["matrix"].detach(),
+                                                       relative=args.relative, full_pred=outs["loss_pred"])
+            accum = getattr(args, "accum_iter", 1)
+            x_vis_d, pos_full_d = outs["features"], outs["pos_full"]   # segment 1 | segment 0 boundary (detached leaves)
+            p0 = self.seg_params[0]
+            seed = _const_scalar(loss.device, 1.0 / accum)             # two roots seeded with 1 / accum: no sum, division, ones_like
+            g = torch.autograd.grad([loss, loss_learn], p0 + [x_vis_d, pos_full_d], grad_outputs=[seed, seed], allow_unused=True)
+            self._store(0, g[:len(p0)])
+            self._cut1 = outs["cut"] + (g[len(p0)], g[len(p0) + 1])
+            self._cut2 = (tokens, pos_all, tokens_d, pos_all_d)
+            return {"loss": loss.detach(), "loss_learn": loss_learn.detach(), "loss_chfr": loss_chfr.detach(),
+                    "loss_mse": loss_mse.detach(), "mask": bool_masked_pos, "matrix": loss_outs["matrix"].detach(),
+                    "teacher_loss_pred": outs_ema["loss_pred"]}
+        if k == 1:
+            x_vis, pos_full, gx, gp = self._cut1
+            tokens_d, pos_all_d = self._cut2[2], self._cut2[3]
+            p1 = self.seg_params[1]
+            outs = [t for t, gt in ((x_vis, gx), (pos_full, gp)) if gt is not None]
+            gouts = [gt for gt in (gx, gp) if gt is not None]
+            g = torch.autograd.grad(outs, p1 + [tokens_d, pos_all_d], grad_outputs=gouts, allow_unused=True)   # (no fused.async_wgrad
+            # region around a segment: measured 7.98 vs 7.87 ms with one around this one, profiles/NEGATIVE_RESULTS.md round 4)
+            self._store(1, g[:len(p1)])
+            self._cut3 = (g[len(p1)], g[len(p1) + 1])
+            return None
         tokens, pos_all = self._cut2[0], self._cut2[1]
         gt, gp = self._cut3
         p2 = self.seg_params[2]
@@ -820,66 +703,24 @@ class SegmentedDDPStep:
         gouts = [q for q in (gt, gp) if q is not None]
         g = torch.autograd.grad(outs, p2, grad_outputs=gouts, allow_unused=True)
         self._store(2, g)
-
-    def _reduce(self, seg):
-        """async all-reduce (mean) of one segment's range of the flat gradient buffer on the process group's stream."""
-        if not dist.is_initialized():
-            return None
-        lo, hi = self.opt.segment_ranges[seg]
-        buf = self.opt.G[lo:hi]
-        w = dist.all_reduce(buf, op=dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM, group=self.group, async_op=True)
-        return (w, buf)
-
-    def _wait(self, works):
-        for item in works:
-            if item is None:
-                continue
-            w, buf = item
-            w.wait()
-            if not self._avg and self.world > 1:
-                buf.div_(self.world)
-
-    def _run(self, phases, update):
-        """phases: three callables (graph replays or the eager segment functions).  accum_iter == 1: each segment's collective is
-        issued right behind its phase; accum_iter > 1: gradients join the window's sum, collectives only when `update`."""
-        if self.accum == 1:
-            works = []
-            for k in range(3):
-                phases[k]()
-                works.append(self._reduce(k))
-            self._wait(works)
-            return True
-        for k in range(3):
-            phases[k]()
-        self.opt.accumulate(last=update)
-        if update:
-            self._wait([self._reduce(k) for k in range(3)])
-        return update
+        return None
 
     def _eager(self, samples, update=True):
         res = {}
-        done = self._run([lambda: res.update(self._phase1(samples)), self._phase2, self._phase3], update)
+        done = self._run([lambda: res.update(self._segment(0, samples)), lambda: self._segment(1), lambda: self._segment(2)], update)
         self._cut1 = self._cut2 = self._cut3 = None      # eager: let the autograd graph go (captured graphs keep theirs alive)
-        if done:
-            self.opt.mark_grads_filled()
-            res["grad_norm"] = step_update(self.model, self.ema, self.opt)
-        else:
-            res["grad_norm"] = None
+        res["grad_norm"] = self._update() if done else None
         return res
 
     def __call__(self, samples, mask_noise=None, update=True):
+        """update=False (gradient accumulation, not the last micro-batch of its window): the returned grad_norm is None."""
         if self.static_noise is not None:
             self.static_noise.copy_(mask_noise, non_blocking=True)
         broadcast_buffers(self.raw, group=self.group)      # DDP's per-forward BatchNorm-buffer broadcast from rank 0
         if self.graphs is None:
             return self._eager(samples, update)
         self.static_in.copy_(samples, non_blocking=True)
-        if self._run([g.replay for g in self.graphs[:3]], update):
-            self.graphs[3].replay()
-            return self.out
-        out = dict(self.out)
-        out["grad_norm"] = None
-        return out
+        return self._replay(update)
 
 
 # --------------------------------------------------------------------------- the epoch loop

@@ -24,7 +24,6 @@ level-0 token embed runs on embed.EmbedFn, every Linear on heads.LinearBiasFn; L
 PyTorch modules.
 """
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
@@ -32,6 +31,7 @@ from . import models_mae_learn_loss as M
 from . import ops
 from . import streams
 from .hierarchical_group import HierarchicalGroup
+from .segmented import SegmentedStep, broadcast_buffers
 
 
 FUSED_EMBED0 = True
@@ -601,21 +601,17 @@ class GraphedM2AEStep:
 
     def __init__(self, model, model_ema, optimizer, args, example, epoch, augment=True, inject_mask_noise=False, warmup_iters=2,
                  generator=None):
-        self.model, self.ema, self.opt, self.args, self.epoch, self.augment = model, model_ema, optimizer, args, epoch, augment
-        self.generator = generator
+        self.model, self.ema, self.opt, self.args, self.epoch = model, model_ema, optimizer, args, epoch
         raw = model.module if hasattr(model, "module") else model
-        dev = example.device
-        self._init_staging(example, raw, inject_mask_noise)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup_iters):
-                if generator is None:
-                    pretrain_step(model, model_ema, optimizer, self.static_in.clone(), epoch, args, mask_noise=self.static_noise, augment=augment)
-                else:
-                    staged = group_stage(model_ema.ema.group_divider, self.static_in.clone(), augment=augment, generator=generator)
-                    pretrain_step(model, model_ema, optimizer, None, epoch, args, mask_noise=self.static_noise, staged=staged)
-        torch.cuda.current_stream().wait_stream(side)
+        self._init_staging(example, raw, inject_mask_noise, augment, generator)
+
+        def warm():
+            if generator is None:
+                pretrain_step(model, model_ema, optimizer, self.static_in.clone(), epoch, args, mask_noise=self.static_noise, augment=augment)
+            else:
+                staged = group_stage(model_ema.ema.group_divider, self.static_in.clone(), augment=augment, generator=generator)
+                pretrain_step(model, model_ema, optimizer, None, epoch, args, mask_noise=self.static_noise, staged=staged)
+        streams.warm_up(warm, warmup_iters, device=example.device)
         torch.cuda.synchronize()
         staged = self._capture_grouping(model_ema.ema.group_divider)
         self.train_graph = torch.cuda.CUDAGraph()
@@ -623,7 +619,8 @@ class GraphedM2AEStep:
             self.out = pretrain_step(model, model_ema, optimizer, None, epoch, args, mask_noise=self.static_noise, staged=staged)
         torch.cuda.synchronize()
 
-    def _init_staging(self, example, raw, inject_mask_noise):
+    def _init_staging(self, example, raw, inject_mask_noise, augment, generator):
+        self.augment, self.generator = augment, generator
         dev = example.device
         self.static_in = example.clone()
         self.static_noise = torch.rand(example.shape[0], raw.num_group, device=dev) if inject_mask_noise else None
@@ -677,10 +674,10 @@ class GraphedM2AEStep:
         return self.out
 
 
-class SegmentedM2AEStep(GraphedM2AEStep):
-    """Data-parallel Point-M2AE step with the gradient all-reduce hidden behind backward (engine_pretrain.SegmentedDDPStep for this
-    model): the grouping graph with look-ahead of GraphedM2AEStep, then SIX hipGraphs with eager collectives between them (no
-    collective is captured):
+class SegmentedM2AEStep(GraphedM2AEStep, SegmentedStep):
+    """Data-parallel Point-M2AE step with the gradient all-reduce hidden behind backward (segmented.SegmentedStep, like
+    engine_pretrain.SegmentedDDPStep): the grouping graph with look-ahead of GraphedM2AEStep, then FIVE hipGraphs with eager
+    collectives between them (no collective is captured):
 
         graph 0  teacher, mask, student forward, backward of the decoder side (segment 0)  -> all-reduce (async) of segment 0
         graph 1  backward of level 2 (segment 1)                                              -> all-reduce (async) of segment 1
@@ -702,47 +699,21 @@ class SegmentedM2AEStep(GraphedM2AEStep):
 
     def __init__(self, model, model_ema, optimizer, args, example, epoch, augment=True, inject_mask_noise=False, warmup_iters=2,
                  generator=None, process_group=None, use_graphs=True, broadcast=True):
-        from . import engine_pretrain as E
         if getattr(args, "accum_iter", 1) > 1:
             raise NotImplementedError("SegmentedM2AEStep runs accum_iter = 1 (config_Point_M2AE.yaml: step_per_update 1)")
         ranges = getattr(optimizer, "segment_ranges", None)
         if ranges is None or sorted(ranges) != list(range(self.NSEG)):
             raise ValueError("SegmentedM2AEStep needs FlatAdamWEma built with segment_of=point_m2ae.ddp_segment "
                              "(engine_pretrain_m2ae.build_optimizer(..., segmented=True))")
-        self.model, self.ema, self.opt, self.args, self.epoch, self.augment = model, model_ema, optimizer, args, epoch, augment
-        self.generator = generator
-        self.raw = model.module if hasattr(model, "module") else model
-        self.group = process_group
-        self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
-        self._avg = dist.is_initialized() and dist.get_backend(process_group) == "nccl" and self.world > 1   # as SegmentedDDPStep
-        if broadcast:
-            E.broadcast_state(self.raw, model_ema, optimizer, group=process_group)
-        self._init_staging(example, self.raw, inject_mask_noise)
-        views = dict((id(p), g) for p, g in optimizer.flat_grad_views())
-        self.seg_params = {sg: list(ps) for sg, ps in optimizer.segment_params.items()}
-        self.seg_views = {sg: [views[id(p)] for p in ps] for sg, ps in self.seg_params.items()}
+        SegmentedStep.__init__(self, model, model_ema, optimizer, args, epoch, process_group, broadcast)
+        self._init_staging(example, self.raw, inject_mask_noise, augment, generator)
         self._cuts = self._grads = None
-        self.graphs = None
         if not use_graphs:
             return
         if warmup_iters:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup_iters):
-                    self._eager(self.static_in.clone())
-            torch.cuda.current_stream().wait_stream(side)
+            streams.warm_up(lambda: self._eager(self.static_in.clone()), warmup_iters)
         torch.cuda.synchronize()
-        staged = self._capture_grouping(model_ema.ema.group_divider)
-        mode = "thread_local" if dist.is_initialized() else "global"
-        self.graphs = [torch.cuda.CUDAGraph() for _ in range(self.NSEG + 1)]
-        with streams.capture(self.graphs[0], capture_error_mode=mode):
-            self.out = self._segment(0, staged)
-        for k in range(1, self.NSEG):
-            with streams.capture(self.graphs[k], pool=self.graphs[0].pool(), capture_error_mode=mode):
-                self._segment(k)
-        with streams.capture(self.graphs[self.NSEG], pool=self.graphs[0].pool(), capture_error_mode=mode):
-            self.out["grad_norm"] = self._update()
+        self._capture(self._capture_grouping(model_ema.ema.group_divider))
         torch.cuda.synchronize()
 
     # ---- the four backward segments -----------------------------------------------------------------------------------------
@@ -763,7 +734,6 @@ class SegmentedM2AEStep(GraphedM2AEStep):
         Segment 0 runs the forward first; segment k > 0 starts from the gradient of level (3 - k)'s output."""
         from contextlib import nullcontext
         from . import fused
-        from . import engine_pretrain as E
         out = None
         ps = self.seg_params[k]
         if k == 0:
@@ -778,7 +748,7 @@ class SegmentedM2AEStep(GraphedM2AEStep):
         region = fused.async_wgrad(dev, defer_heads=True) if DEFER_WGRADS and dev.type == "cuda" else nullcontext()
         with region:
             g = torch.autograd.grad(roots, ps + leaves, grad_outputs=gouts, allow_unused=True)
-        E.SegmentedDDPStep._store(self, k, g[:len(ps)])
+        self._store(k, g[:len(ps)])
         gl = g[len(ps):]
         if k == 0:
             self._grads = {2: gl[0], 1: gl[1]}
@@ -793,26 +763,6 @@ class SegmentedM2AEStep(GraphedM2AEStep):
             return {k_: (v.detach() if torch.is_tensor(v) else v) for k_, v in out.items()}
         return None
 
-    def _update(self):
-        from . import engine_pretrain as E
-        self.opt.mark_grads_filled()
-        return E.step_update(self.model, self.ema, self.opt)
-
-    def _reduce(self, seg):
-        from . import engine_pretrain as E
-        return E.SegmentedDDPStep._reduce(self, seg)
-
-    def _wait(self, works):
-        from . import engine_pretrain as E
-        E.SegmentedDDPStep._wait(self, works)
-
-    def _run(self, phases):
-        works = []
-        for k in range(self.NSEG):
-            phases[k]()
-            works.append(self._reduce(k))
-        self._wait(works)
-
     def _eager(self, pts):
         staged = group_stage(self.ema.ema.group_divider, pts, augment=self.augment, generator=self.generator)
         res = {}
@@ -824,13 +774,10 @@ class SegmentedM2AEStep(GraphedM2AEStep):
     def __call__(self, pts, mask_noise=None, next_pts=None, update=True):
         if not update:
             raise NotImplementedError("SegmentedM2AEStep runs accum_iter = 1")
-        from . import engine_pretrain as E
-        E.broadcast_buffers(self.raw, group=self.group)      # DDP's per-forward BatchNorm-buffer broadcast from rank 0
+        broadcast_buffers(self.raw, group=self.group)      # DDP's per-forward BatchNorm-buffer broadcast from rank 0
         if self.graphs is None:
             if self.static_noise is not None and mask_noise is not None:
                 self.static_noise.copy_(mask_noise, non_blocking=True)
             return self._eager(pts)
         self._take_staged(pts, mask_noise, next_pts)
-        self._run([g.replay for g in self.graphs[:self.NSEG]])
-        self.graphs[self.NSEG].replay()
-        return self.out
+        return self._replay()

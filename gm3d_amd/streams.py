@@ -96,3 +96,14 @@ def capture(graph, **kw):
                 raise RuntimeError("hipGraph capture would end with %d unjoined side stream(s): %s -- every stream forked "
                                    "inside a capture must be joined (gm3d_amd.streams.join) before the capture ends"
                                    % (len(left), "; ".join(w for _, w in left)))
+
+
+def warm_up(fn, iters, device=None):
+    """fn() `iters` times on a fresh side stream that waits for the current stream and is waited for by it: the eager iterations
+    before a capture (lazy initialisation, library workspaces, code objects).  The caller synchronises."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(iters):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)

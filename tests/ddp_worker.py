@@ -52,9 +52,9 @@ def run(rank, world, port, out, B=4, steps=3):
         # step of graph mode is compared with eager execution, not with itself
         seg.static_noise.copy_(noise[0][ids].cuda())
         bufs = [t.detach().clone() for t in m.buffers()]
-        seg._phase1(data[0][ids].cuda())
-        seg._phase2()
-        seg._phase3()
+        seg._segment(0, data[0][ids].cuda())
+        seg._segment(1)
+        seg._segment(2)
         seg._cut1 = seg._cut2 = seg._cut3 = None
         with torch.no_grad():                               # the extra forward moved the BatchNorm running statistics: roll back
             for t, v in zip(m.buffers(), bufs):
@@ -123,9 +123,9 @@ def full_size_leg(rank, world, out, E, M, clouds, args, B=128, steps=3):
                              use_graphs=True)
     seg.static_noise.copy_(noise[0][ids].cuda())
     bufs = [t.detach().clone() for t in m.buffers()]
-    seg._phase1(data[0][ids].cuda())          # this rank's shard alone, EAGERLY, no collectives
-    seg._phase2()
-    seg._phase3()
+    seg._segment(0, data[0][ids].cuda())      # this rank's shard alone, EAGERLY, no collectives
+    seg._segment(1)
+    seg._segment(2)
     seg._cut1 = seg._cut2 = seg._cut3 = None
     with torch.no_grad():
         for t, v in zip(m.buffers(), bufs):

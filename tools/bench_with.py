@@ -8,7 +8,7 @@ cut = args.index("--") if "--" in args else len(args)
 for item in args[:cut]:
     name, val = item.split("=")
     mod, attr = name.rsplit(".", 1)
-    parts, obj = mod.split("."), None          # engine_pretrain.SegmentedDDPStep._reduce=... : module first, then attributes of it
+    parts, obj = mod.split("."), None          # segmented.SegmentedStep._reduce=... (both models' steps): module first, then attributes of it
     for cutp in range(len(parts), 0, -1):
         try:
             obj = importlib.import_module("gm3d_amd." + ".".join(parts[:cutp]))

@@ -68,9 +68,9 @@ def main():
 
     def eager_once():
         restore()
-        out = seg._phase1(x.clone())
-        seg._phase2()
-        seg._phase3()
+        out = seg._segment(0, x.clone())
+        seg._segment(1)
+        seg._segment(2)
         seg._cut1 = seg._cut2 = seg._cut3 = None
         torch.cuda.synchronize()
         return opt.G.clone(), {k: v.clone() for k, v in out.items() if torch.is_tensor(v)}

@@ -54,9 +54,9 @@ def build(B, graphs):
 
 
 def eager(seg, data):
-    seg._phase1(data)
-    seg._phase2()
-    seg._phase3()
+    seg._segment(0, data)
+    seg._segment(1)
+    seg._segment(2)
     seg._cut1 = seg._cut2 = seg._cut3 = None
 
 

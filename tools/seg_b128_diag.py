@@ -49,9 +49,9 @@ seg = E.SegmentedDDPStep(m, ema, opt, args, data, 200, warmup_iters=int(os.envir
 seg.static_noise.copy_(noise)
 def eager_local():
     bufs = [t.detach().clone() for t in m.buffers()]
-    seg._phase1(data)
-    seg._phase2()
-    seg._phase3()
+    seg._segment(0, data)
+    seg._segment(1)
+    seg._segment(2)
     seg._cut1 = seg._cut2 = seg._cut3 = None
     with torch.no_grad():
         for t, v in zip(m.buffers(), bufs):

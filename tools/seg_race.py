@@ -26,7 +26,7 @@ for it in range(iters):
     x = clouds.gaussian(B, 1024, 100 + it).cuda()
     noise = torch.rand(B, 64, generator=torch.Generator().manual_seed(it)).cuda()
     seg.static_noise.copy_(noise)
-    seg._phase1(x.clone()); seg._phase2(); seg._phase3()
+    seg._segment(0, x.clone()); seg._segment(1); seg._segment(2)
     seg._cut1 = seg._cut2 = seg._cut3 = None
     torch.cuda.synchronize()
     ref = opt.G.clone()
