@@ -145,6 +145,9 @@ SIGNATURES = {
     "gm3d_svm_smo": [_vp, _i, _i, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp],
     "gm3d_svm_weights": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "gm3d_svm_predict": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gm3d_mask_centers": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp],
+    "gm3d_patch_chamfer_l1_loss_fwd": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
+    "gm3d_patch_chamfer_l1_loss_bwd": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp],
 }
 
 

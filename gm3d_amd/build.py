@@ -35,6 +35,7 @@ SOURCES = {
     "vote.hip": [],
     "cls_tail.hip": [],
     "svm.hip": ["-ffp-contract=off"],
+    "mask.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

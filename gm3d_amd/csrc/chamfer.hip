@@ -95,7 +95,10 @@ __global__ __launch_bounds__(256) void chamfer32_bwd_kernel(const float* __restr
 // output (any float type, batch-strided view) and its target patch through the id list, keeps the 32x32 pair tile in readlanes like
 // chamfer32_fwd_kernel (identical distance arithmetic and argmin rule), and writes the patch mean; a one-block kernel finishes the
 // scalar.  The backward writes d(mean)/d(pred) in pred's type from the saved argmins.
-template <class T>
+// L1 = true: plain Point-MAE's `cdl1` (models/Point_MAE.py:391-392, ChamferDistanceL1 = (mean(sqrt d1) + mean(sqrt d2)) / 2): the same
+// pair tile and argmins, the per-patch value is (sum sqrt d1 + sum sqrt d2) / 64, and the backward carries sqrt's 1 / (2 sqrt d) --
+// unguarded, as torch.sqrt's backward in ops.ChamferDistanceL1 is: a predicted point that coincides with its neighbour gets inf * 0.
+template <class T, bool L1 = false>
 __global__ __launch_bounds__(256) void patch_loss_fwd_kernel(const T* __restrict__ pred, size_t pred_bstride,
                                                              const float* __restrict__ target, const long long* __restrict__ ids,
                                                              size_t ids_bstride, int B, int Tn, int M, float* __restrict__ matrix,
@@ -127,10 +130,11 @@ __global__ __launch_bounds__(256) void patch_loss_fwd_kernel(const T* __restrict
     }
     const size_t o = (size_t)p * 32 + l;
     if (first) i1[o] = bi; else i2[o] = bi;
+    if constexpr (L1) best = sqrtf(best);
     float s = __fadd_rn(best, __shfl(best, lane ^ 32));          // d1[l] + d2[l] on both halves
 #pragma unroll
     for (int w = 16; w > 0; w >>= 1) s = __fadd_rn(s, __shfl_xor(s, w));
-    if (lane == 0) matrix[p] = s * (1.0f / 32.0f);
+    if (lane == 0) matrix[p] = s * (L1 ? 1.0f / 64.0f : 1.0f / 32.0f);
 }
 
 // mean of n values, one block, fixed order (thread-strided partial sums, then a tree)
@@ -147,7 +151,7 @@ __global__ __launch_bounds__(256) void mean_small_kernel(const float* __restrict
     if (threadIdx.x == 0) out[0] = red[0] / (float)n;
 }
 
-template <class T>
+template <class T, bool L1 = false>
 __global__ __launch_bounds__(256) void patch_loss_bwd_kernel(const T* __restrict__ pred, size_t pred_bstride,
                                                              const float* __restrict__ target, const long long* __restrict__ ids,
                                                              size_t ids_bstride, const int32_t* __restrict__ i1,
@@ -177,11 +181,15 @@ __global__ __launch_bounds__(256) void patch_loss_bwd_kernel(const T* __restrict
         mx = tp[0]; my = tp[1]; mz = tp[2];
     }
     // d mean / d (d1 | d2)[point] = (g / (B M)) / 32: the two divisions autograd makes for mean() of mean(dim=-1)
-    const float g = (gmean[0] / (float)(B * M)) / 32.0f;
+    float g = (gmean[0] / (float)(B * M)) / 32.0f;
     const size_t o = (size_t)p * 32 + l;
     const int j = first ? i1[o] : i2[o];
     const int src = first ? 32 + j : j;
     const float ox = __shfl(mx, src), oy = __shfl(my, src), oz = __shfl(mz, src);
+    if constexpr (L1) {
+        // autograd's chain for (mean(sqrt d1) + mean(sqrt d2)) / 2: g / 2, / (B M 32), / (2 sqrt d); d recomputed as the forward formed it
+        g = ((gmean[0] / 2.0f) / (float)(B * M * 32)) / (2.0f * sqrtf(sqdist3(mx, my, mz, ox, oy, oz)));
+    }
     const float tx = __fmul_rn(__fmul_rn(2.0f, __fsub_rn(mx, ox)), g);
     const float ty = __fmul_rn(__fmul_rn(2.0f, __fsub_rn(my, oy)), g);
     const float tz = __fmul_rn(__fmul_rn(2.0f, __fsub_rn(mz, oz)), g);
@@ -447,4 +455,49 @@ extern "C" int gm3d_patch_chamfer_loss_bwd(const void* pred, long long pred_bstr
                                            long long ids_bstride, const int32_t* idx1, const int32_t* idx2, const float* gmean, int B,
                                            int T, int M, void* dpred, int dtype, gm3d_stream_t stream) {
     return gm3d_patch_chamfer_loss_bwd_full(pred, pred_bstride, target, ids, ids_bstride, idx1, idx2, gmean, B, T, M, 0, dpred, dtype, stream);
+}
+
+extern "C" int gm3d_patch_chamfer_l1_loss_fwd(const void* pred, long long pred_bstride, const float* target, const long long* ids,
+                                              long long ids_bstride, int B, int T, int M, float* matrix, int32_t* idx1, int32_t* idx2,
+                                              float* mean_out, int dtype, gm3d_stream_t stream) {
+    using namespace gm3d;
+    if (!pred || !target || !ids || !matrix || !idx1 || !idx2 || !mean_out || B < 0 || T < 1 || M < 1 || M > T) return GM3D_EINVAL;
+    if (pred_bstride < (long long)M * 96 || ids_bstride < M) return GM3D_EINVAL;
+    if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
+    if ((long long)B * M > 0x3ffffffLL) return GM3D_EUNSUPPORTED;      // B * M * 32 is formed in int
+    if (B == 0) return GM3D_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int P = B * M;
+    const auto kb = patch_loss_fwd_kernel<bf16_t, true>;
+    const auto kf = patch_loss_fwd_kernel<float, true>;
+    GM3D_CH_DISPATCH(dtype,
+                  hipLaunchKernelGGL(kb, dim3((P + 3) / 4), dim3(256), 0, st, (const bf16_t*)pred, (size_t)pred_bstride, target, ids,
+                                     (size_t)ids_bstride, B, T, M, matrix, idx1, idx2),
+                  hipLaunchKernelGGL(kf, dim3((P + 3) / 4), dim3(256), 0, st, (const float*)pred, (size_t)pred_bstride, target, ids,
+                                     (size_t)ids_bstride, B, T, M, matrix, idx1, idx2));
+    hipLaunchKernelGGL(mean_small_kernel, dim3(1), dim3(256), 0, st, matrix, P, mean_out);
+    GM3D_CHECK_LAUNCH();
+    return GM3D_OK;
+}
+
+extern "C" int gm3d_patch_chamfer_l1_loss_bwd(const void* pred, long long pred_bstride, const float* target, const long long* ids,
+                                              long long ids_bstride, const int32_t* idx1, const int32_t* idx2, const float* gmean, int B,
+                                              int T, int M, void* dpred, int dtype, gm3d_stream_t stream) {
+    using namespace gm3d;
+    if (!pred || !target || !ids || !idx1 || !idx2 || !gmean || !dpred || B < 0 || T < 1 || M < 1 || M > T) return GM3D_EINVAL;
+    if (pred_bstride < (long long)M * 96 || ids_bstride < M) return GM3D_EINVAL;
+    if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
+    if ((long long)B * M > 0x3ffffffLL) return GM3D_EUNSUPPORTED;
+    if (B == 0) return GM3D_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int P = B * M;
+    const auto kb = patch_loss_bwd_kernel<bf16_t, true>;
+    const auto kf = patch_loss_bwd_kernel<float, true>;
+    GM3D_CH_DISPATCH(dtype,
+                  hipLaunchKernelGGL(kb, dim3((P + 3) / 4), dim3(256), 0, st, (const bf16_t*)pred, (size_t)pred_bstride, target, ids,
+                                     (size_t)ids_bstride, idx1, idx2, gmean, B, T, M, (bf16_t*)dpred, 0),
+                  hipLaunchKernelGGL(kf, dim3((P + 3) / 4), dim3(256), 0, st, (const float*)pred, (size_t)pred_bstride, target, ids,
+                                     (size_t)ids_bstride, idx1, idx2, gmean, B, T, M, (float*)dpred, 0));
+    GM3D_CHECK_LAUNCH();
+    return GM3D_OK;
 }

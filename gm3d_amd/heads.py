@@ -745,6 +745,40 @@ class PatchChamferLossFn(torch.autograd.Function):
         return dpred, None, None, None
 
 
+class PatchChamferL1LossFn(torch.autograd.Function):
+    """ChamferDistanceL1 of plain Point-MAE (`cdl1`) on the masked patches in one pass: the arguments of PatchChamferLossFn
+    -> ((mean(sqrt d1) + mean(sqrt d2)) / 2 over the B * M patches, the per-patch values (B,M) f32)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, mask_ids):
+        ctx.set_materialize_grads(False)
+        B, M, _ = pred.shape
+        dev = pred.device
+        matrix = torch.empty(B, M, dtype=torch.float32, device=dev)
+        i1 = torch.empty(B * M, 32, dtype=torch.int32, device=dev)
+        i2 = torch.empty(B * M, 32, dtype=torch.int32, device=dev)
+        mean = torch.empty((), dtype=torch.float32, device=dev)
+        _launch("gm3d_patch_chamfer_l1_loss_fwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_l1_loss_fwd,
+                _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), B, target.shape[1], M, _ptr(matrix),
+                _ptr(i1), _ptr(i2), _ptr(mean), _DT[pred.dtype], _stream())
+        ctx.save_for_backward(pred, target, mask_ids, i1, i2)
+        ctx.mark_non_differentiable(matrix)
+        return mean, matrix
+
+    @staticmethod
+    def backward(ctx, g, _gm):
+        pred, target, mask_ids, i1, i2 = ctx.saved_tensors
+        B, M, _ = pred.shape
+        if g is None:
+            return None, None, None
+        g = g.detach().reshape(1).float().contiguous()
+        dpred = torch.empty(B, M, 96, dtype=pred.dtype, device=pred.device)
+        _launch("gm3d_patch_chamfer_l1_loss_bwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_l1_loss_bwd,
+                _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), _ptr(i1), _ptr(i2), _ptr(g), B,
+                target.shape[1], M, _ptr(dpred), _DT[pred.dtype], _stream())
+        return dpred, None, None
+
+
 FUSED_PATCH_LOSS = True
 
 
@@ -847,3 +881,22 @@ def token_assemble(tokens, pos, vis_ids, mask_ids, order=None):
         else:
             order = torch.cat([vis_ids, mask_ids], dim=1)
     return TokenAssembleFn.apply(tokens, pos, order, vis_ids.shape[1])
+
+
+@torch.no_grad()
+def mask_centers(keys, num_mask, start=None):
+    """Centre masking of plain Point-MAE in one launch (gm3d_mask_centers): keys = noise (B,G) f32 (rand: the num_mask smallest are
+    masked) or, with start (B) int32, center (B,G,3) f32 (block: the num_mask centres nearest to center[b, start[b]]).
+    -> (mask (B,G) bool, order (B,G) int64 = [visible ids ascending | masked ids ascending]).  G <= 512."""
+    keys = keys.detach().float().contiguous()
+    B, G = keys.shape[:2]
+    mode = 0 if start is None else 1
+    if keys.dim() != (2 if mode == 0 else 3) or (mode == 1 and keys.shape[2] != 3):
+        raise RuntimeError("mask_centers takes noise (B,G), or center (B,G,3) with start (B)")
+    if start is not None:
+        start = start.to(keys.device, torch.int32).contiguous()
+    mask = torch.empty(B, G, dtype=torch.bool, device=keys.device)
+    order = torch.empty(B, G, dtype=torch.int64, device=keys.device)
+    _launch("gm3d_mask_centers", {"B": B, "G": G, "mode": mode}, lib.gm3d_mask_centers, _ptr(keys), _ptr(start), mode, B, G,
+            int(num_mask), _ptr(mask), _ptr(order), G, _stream())
+    return mask, order

@@ -60,11 +60,34 @@ class MaskTransformer(nn.Module):
         mask.scatter_(1, idx, True)
         return mask
 
-    def forward(self, neighborhood, center, noaug=False):
+    device_mask = False      # True: the mask and the id lists come from gm3d_mask_centers (no host shuffle, no host-to-device copy)
+
+    def select(self, center, noaug=False, mask_noise=None, mask_start=None, mask=None):
+        """-> (mask (B,G) bool, vis_ids, mask_ids, on_device).  An explicit `mask` overrides everything.  With device_mask (or
+        injected draws) on a GPU the two id lists are the halves of gm3d_mask_centers' [visible | masked] order and nothing here
+        talks to the host: mask_noise (B,G) f32 ranks the groups of `rand`, mask_start (B) int32 names the start centres of
+        `block`; draws that are not given come from torch.rand / torch.randint on the device (graph-safe Philox, like
+        generate_mask's noise).  Otherwise: the reference's host-side draw."""
+        B, G, _ = center.shape
+        off = noaug or self.mask_ratio == 0
+        num_mask = 0 if off else int(self.mask_ratio * G)
+        if mask is not None:
+            mask = mask.to(center.device, torch.bool)
+            return (mask,) + split_ids(mask, G - num_mask) + (False,)
+        if center.is_cuda and not off and (self.device_mask or mask_noise is not None or mask_start is not None):
+            from . import heads
+            if self.mask_type == "rand":
+                noise = torch.rand(B, G, device=center.device) if mask_noise is None else mask_noise
+                mask, order = heads.mask_centers(noise, num_mask)
+            else:
+                start = (torch.randint(0, G, (B,), device=center.device, dtype=torch.int32) if mask_start is None else mask_start)
+                mask, order = heads.mask_centers(center, num_mask, start=start)
+            return mask, order[:, :G - num_mask], order[:, G - num_mask:], True
         mask = (self._mask_center_rand if self.mask_type == "rand" else self._mask_center_block)(center, noaug=noaug)
-        G = center.shape[1]
-        num_vis = G if (noaug or self.mask_ratio == 0) else G - int(self.mask_ratio * G)
-        vis_ids, _ = split_ids(mask, num_vis)
+        return (mask,) + split_ids(mask, G - num_mask) + (False,)
+
+    def forward(self, neighborhood, center, noaug=False, mask_noise=None, mask_start=None, mask=None):
+        mask, vis_ids, _, _ = self.select(center, noaug, mask_noise, mask_start, mask)
         tokens = self.encoder(neighborhood)
         pos = _pos_mlp(self.pos_embed, center)
         return self.blocks(take(tokens, vis_ids), take(pos, vis_ids), norm=self.norm), mask
@@ -106,20 +129,40 @@ class Point_MAE(nn.Module):
             return heads.LinearBiasFn.apply(x_rec, c.weight, c.bias, heads._adt())
         return nn.functional.linear(x_rec, c.weight.squeeze(-1), c.bias)
 
-    def forward(self, pts, noaug=False, vis=False, **kwargs):
-        """P/:391-441 (Point-MAE pre-training loss; `vis` is a plotting aid and is not provided)."""
+    def forward(self, pts, noaug=False, vis=False, mask_noise=None, mask_start=None, mask=None, **kwargs):
+        """P/:391-441 (Point-MAE pre-training loss; `vis` is a plotting aid and is not provided).  mask / mask_noise / mask_start:
+        see MaskTransformer.select.  With any of them (or MAE_encoder.device_mask) on a GPU the step is the replayable one:
+        token and position gathers through heads.token_assemble / pos_assemble, the loss through the fused patch kernels."""
         neighborhood, center, _ = self.group_divider(pts)
-        x_vis, mask = self.MAE_encoder(neighborhood, center, noaug=noaug)
-        B, V, C = x_vis.shape
+        enc = self.MAE_encoder
         if noaug:
-            return x_vis
-        vis_ids, mask_ids = split_ids(mask, V)
+            return enc(neighborhood, center, noaug=True)[0]
+        chosen = mask is not None or mask_noise is not None or mask_start is not None or enc.device_mask
+        mask, vis_ids, mask_ids, _ = enc.select(center, False, mask_noise, mask_start, mask)
+        B, N = mask_ids.shape
+        tokens = enc.encoder(neighborhood)
+        pos = _pos_mlp(enc.pos_embed, center)
         dpos = _pos_mlp(self.decoder_pos_embed, center)
-        N = mask_ids.shape[1]
-        x_full = torch.cat([x_vis, self.mask_token.expand(B, N, -1).to(x_vis.dtype)], dim=1)
-        pos_full = torch.cat([take(dpos, vis_ids), take(dpos, mask_ids)], dim=1)
+        if chosen and M.FUSED_HEADS and pts.is_cuda:
+            from . import heads
+            tok_vis, pos_vis, _ = heads.token_assemble(tokens, pos, vis_ids, mask_ids)
+            _, pos_full = heads.pos_assemble(dpos, vis_ids, mask_ids, dt=tok_vis.dtype)
+            x_vis = enc.blocks(tok_vis, pos_vis, norm=enc.norm)
+            x_full = torch.cat([x_vis, heads.ExpandRowsFn.apply(self.mask_token, B, N, x_vis.dtype)], dim=1)
+        else:
+            x_vis = enc.blocks(take(tokens, vis_ids), take(pos, vis_ids), norm=enc.norm)
+            x_full = torch.cat([x_vis, self.mask_token.expand(B, N, -1).to(x_vis.dtype)], dim=1)
+            pos_full = torch.cat([take(dpos, vis_ids), take(dpos, mask_ids)], dim=1)
         x_rec = self.MAE_decoder(x_full, pos_full, N)[:, -N:]          # P/:212: only the masked tokens are decoded to points
-        rebuild = self._points(x_rec).reshape(B * N, -1, 3).float()
+        pred = self._points(x_rec)
+        if chosen and M.FUSED_HEADS:
+            from . import heads
+            pred = pred.contiguous()
+            if heads.patch_chamfer_loss_supported(pred, neighborhood, mask_ids):
+                # cdl2: mean(d1) + mean(d2) over equal-sized patches = the mean of the per-point d1 + d2 the GM3D loss kernel forms
+                fn = heads.PatchChamferLossFn if self.loss == "cdl2" else heads.PatchChamferL1LossFn
+                return fn.apply(pred, neighborhood, mask_ids)[0]
+        rebuild = pred.reshape(B * N, -1, 3).float()
         gt = take(neighborhood, mask_ids).reshape(B * N, -1, 3)
         return self.loss_func(rebuild, gt)
 

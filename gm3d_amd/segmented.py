@@ -76,7 +76,8 @@ def step_update(model, model_ema, optimizer, clip_grad=5.0):
     raw = model.module if hasattr(model, "module") else model
     if hasattr(optimizer, "flat_grad_views"):      # FlatAdamWEma: clip + AdamW + EMA(params) + bf16 shadows, one pass
         grad_norm = optimizer.step()
-        model_ema.update(raw)                      # BatchNorm buffers only
+        if model_ema is not None:                  # (plain Point-MAE pre-training has no teacher)
+            model_ema.update(raw)                  # BatchNorm buffers only
         return grad_norm
     grad_norm = torch.nn.utils.clip_grad_norm_(raw.parameters(), clip_grad, foreach=True)
     optimizer.step()

@@ -134,6 +134,18 @@ int gm3d_patch_chamfer_loss_bwd(const void *pred, long long pred_bstride, const 
 int gm3d_patch_chamfer_loss_bwd_full(const void *pred, long long pred_bstride, const float *target, const long long *ids,
                                      long long ids_bstride, const int32_t *idx1, const int32_t *idx2, const float *gmean, int B, int T,
                                      int M, int lead, void *dpred, int dtype, gm3d_stream_t stream);
+/* The same pass for plain Point-MAE's `cdl1` loss (models/Point_MAE.py:391-392,426: ChamferDistanceL1 on the masked patches =
+ * (mean(sqrt d1) + mean(sqrt d2)) / 2 over the B * M patches x 32 points).  Same arguments as gm3d_patch_chamfer_loss_fwd / _bwd;
+ * matrix (B, M) = the per-patch value (sum sqrt d1 + sum sqrt d2) / 64, mean_out its mean, summed in a fixed order.  Argmins
+ * bit-identical to gm3d_chamfer_fwd.  The backward multiplies by sqrt's 1 / (2 sqrt d) with no guard at d = 0, like torch.sqrt's
+ * backward in the unfused form (a predicted point exactly on its neighbour gives inf * 0).  B == 0 returns GM3D_OK launching
+ * nothing; B * M <= 2^26 - 1 (GM3D_EUNSUPPORTED beyond). */
+int gm3d_patch_chamfer_l1_loss_fwd(const void *pred, long long pred_bstride, const float *target, const long long *ids,
+                                   long long ids_bstride, int B, int T, int M, float *matrix, int32_t *idx1, int32_t *idx2,
+                                   float *mean_out, int dtype, gm3d_stream_t stream);
+int gm3d_patch_chamfer_l1_loss_bwd(const void *pred, long long pred_bstride, const float *target, const long long *ids,
+                                   long long ids_bstride, const int32_t *idx1, const int32_t *idx2, const float *gmean, int B, int T,
+                                   int M, void *dpred, int dtype, gm3d_stream_t stream);
 
 /* Plain LayerNorm over (R, C) rows, 4 <= C <= 512, C % 4 == 0 (nn.LayerNorm of the 96 / 192 / 384-wide Point-M2AE levels):
  * h = (x - mean) * rstd * gamma + beta in `dtype`, mean / rstd (R) f32 saved for the backward.  Backward: dx in `dtype`;
@@ -382,6 +394,18 @@ int gm3d_mask_select(const float *loss_pred, const float *noise, int B, int L, i
 /* ... with the mask also as bytes (mask_bool (B,L) 0 / 1 or NULL): bool_masked_pos of engine_pretrain.py:100 without a conversion pass. */
 int gm3d_mask_select_b(const float *loss_pred, const float *noise, int B, int L, int len_keep, int len_loss, float *mask,
                        unsigned char *mask_bool, long long *vis_ids, long long *mask_ids, int id_pitch, gm3d_stream_t stream);
+/* Centre masking of plain Point-MAE pre-training (models/Point_MAE.py:268-317 _mask_center_block / _mask_center_rand) and the id
+ * lists of the boolean-mask indexing behind it, in one launch: the num_mask groups with the smallest (key, index) pairs are masked.
+ * mode 0 (rand): keys_or_center = noise (B,G) f32, start ignored (may be NULL).  mode 1 (block): keys_or_center = center (B,G,3)
+ * f32, start (B) int32 (required); the key of group g is the squared distance to center[b, start[b]], summed x, y, z in fp32
+ * without FMA, so start[b] itself is masked whenever num_mask >= 1 (a start outside 0..G-1 is clamped into it).
+ * Out: mask_bool (B,G) bytes 0 / 1; order (B,id_pitch) int64, id_pitch >= G: columns [0, G-num_mask) = the visible ids ascending,
+ * [G-num_mask, G) = the masked ids ascending (the [visible | masked] permutation gm3d_mask_select writes with an id_pitch and
+ * gm3d_token_assemble_* consume); columns >= G are not written.  A pure function of its inputs (no atomics).
+ * Limits: 1 <= G <= 512 (GM3D_EUNSUPPORTED beyond), 0 <= num_mask < G; NULL pointers, num_mask or id_pitch out of range, or mode 1
+ * without start: GM3D_EINVAL.  B == 0 returns GM3D_OK launching nothing.  All checked on the host before any launch. */
+int gm3d_mask_centers(const float *keys_or_center, const int *start, int mode, int B, int G, int num_mask,
+                      unsigned char *mask_bool, long long *order, int id_pitch, gm3d_stream_t stream);
 /* C (M,N) bf16 = A (M,K) bf16 . W (N,K)^T bf16 (+ bias (N) f32), fp32 accumulation: nn.Linear / Conv1d(k=1) forward with W the
  * weight as stored, input gradient with W the transposed weight.  Row pitches lda / ldw / ldc in elements (multiples of 8).
  * Limits: N % 128 == 0, K % 64 == 0. */
