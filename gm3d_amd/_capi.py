@@ -148,6 +148,9 @@ SIGNATURES = {
     "gm3d_mask_centers": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp],
     "gm3d_patch_chamfer_l1_loss_fwd": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
     "gm3d_patch_chamfer_l1_loss_bwd": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp],
+    "gm3d_knn_probe_normalize": [_vp, _i, _i, _vp, _vp],
+    "gm3d_knn_probe_neighbours": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
+    "gm3d_knn_probe_classify": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp],
 }
 
 

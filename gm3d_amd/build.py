@@ -36,6 +36,7 @@ SOURCES = {
     "cls_tail.hip": [],
     "svm.hip": ["-ffp-contract=off"],
     "mask.hip": ["-ffp-contract=off"],
+    "knn_probe.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

@@ -8,6 +8,9 @@ Differences of execution only: FPS emits the sampled points in the same launch (
 features are pooled on the GPU BEFORE the all-gather (the SVM never sees the un-pooled tokens), which cuts the
 collective from 64x384 to 384 floats per cloud.
 
+probe="knn" / "both" adds the reference's solver-free second probe, the temperature-weighted k-NN vote (evaluate_knn,
+gm3d_amd.knn_probe), on the same gathered features.
+
 svm_backend="hip" solves the same SVC(C=0.01, kernel='linear') problem on the GPU (gm3d_amd.svm.LinearSVC): the gathered,
 pooled features never leave the device.  The default stays sklearn.
 
@@ -103,13 +106,44 @@ def _evaluate_svm_hip(train_features, train_labels, test_features, test_labels):
     return clf.score(pooled(test_features), dev(test_labels, torch.int64))
 
 
+def evaluate_knn(train_features, train_labels, test_features, test_labels, ks=(10, 20, 100, 200), T=0.07):
+    """The reference's second probe (Point-MAE_SA3D/main_knn.py:339-363): the temperature-weighted k-NN vote on L2-normalised
+    features, on the GPU (gm3d_amd.knn_probe).  Accepts token features (n,T,C) or already pooled (n,C), pooled as evaluate_svm pools;
+    labels are class indices.  -> {k: (top-1 %, top-5 %)}; a k above the number of training rows is skipped with a warning."""
+    import warnings
+    from . import knn_probe
+
+    def dev(t, dtype):
+        t = torch.as_tensor(t)
+        return (t if t.is_cuda else t.to("cuda")).to(dtype)
+
+    def prepared(f):
+        f = dev(f, torch.float32)
+        return knn_probe.normalize((pool_features(f) if f.dim() == 3 else f).contiguous())
+    xtr, xte = prepared(train_features), prepared(test_features)
+    ytr, yte = dev(train_labels, torch.int64).view(-1).contiguous(), dev(test_labels, torch.int64).view(-1).contiguous()
+    num_classes = max(int(torch.maximum(ytr.max(), yte.max()).item()) + 1, 2)
+    out = {}
+    for k in ks:
+        if k > xtr.shape[0]:
+            warnings.warn("evaluate_knn: k = %d skipped, only %d training rows" % (k, xtr.shape[0]))
+            continue
+        out[k] = knn_probe.knn_classifier(xtr, ytr, xte, yte, k, T, num_classes)
+    return out
+
+
 @torch.no_grad()
-def validate(model, extra_train_dataloader, test_dataloader, npoints=None, device="cuda", bf16=False, svm_backend="sklearn"):
+def validate(model, extra_train_dataloader, test_dataloader, npoints=None, device="cuda", bf16=False, svm_backend="sklearn",
+             probe="svm", knn_ks=(10, 20, 100, 200), knn_T=0.07):
     """Loaders yield (taxonomy_ids, model_ids, (points, label)) like the reference's ModelNet loaders (:428-431).
     Returns the SVM accuracy (computed on every rank from the gathered features, like the reference).  npoints None:
-    default_npoints(model).  svm_backend "hip" keeps the gathered features on the GPU and solves there."""
+    default_npoints(model).  svm_backend "hip" keeps the gathered features on the GPU and solves there.
+    probe "svm" (default): the SVM accuracy; "knn": evaluate_knn's {k: (top-1 %, top-5 %)} on the same gathered features, no SVM;
+    "both": (SVM accuracy, that dict)."""
     if svm_backend not in ("sklearn", "hip"):
         raise ValueError("unknown SVM backend %r (sklearn or hip)" % (svm_backend,))
+    if probe not in ("svm", "knn", "both"):
+        raise ValueError("unknown probe %r (svm, knn or both)" % (probe,))
     was_training = model.training
     model.eval()
     feats = {}
@@ -121,7 +155,14 @@ def validate(model, extra_train_dataloader, test_dataloader, npoints=None, devic
             l.append(label.view(-1))
         feats[split] = (gather_tensor(torch.cat(f, 0)), gather_tensor(torch.cat(l, 0)))
     model.train(was_training)
+    knn = None
+    if probe != "svm":
+        knn = evaluate_knn(feats["train"][0], feats["train"][1], feats["test"][0], feats["test"][1], ks=knn_ks, T=knn_T)
+        if probe == "knn":
+            return knn
     if svm_backend == "hip":
-        return evaluate_svm(feats["train"][0], feats["train"][1], feats["test"][0], feats["test"][1], backend="hip")
-    return evaluate_svm(feats["train"][0].cpu().numpy(), feats["train"][1].cpu().numpy(),
-                        feats["test"][0].cpu().numpy(), feats["test"][1].cpu().numpy())
+        acc = evaluate_svm(feats["train"][0], feats["train"][1], feats["test"][0], feats["test"][1], backend="hip")
+    else:
+        acc = evaluate_svm(feats["train"][0].cpu().numpy(), feats["train"][1].cpu().numpy(),
+                           feats["test"][0].cpu().numpy(), feats["test"][1].cpu().numpy())
+    return acc if probe == "svm" else (acc, knn)

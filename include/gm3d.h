@@ -731,6 +731,42 @@ int gm3d_svm_weights(const float *X, int n, int d, int ncls, const int *class_st
 int gm3d_svm_predict(const float *X, int m, int d, int ncls, const double *w, const double *rho, const long long *labels,
                      long long *pred, long long *correct, gm3d_stream_t stream);
 
+/* ---- Weighted k-NN probe of pretrained features (gm3d_amd/csrc/knn_probe.hip) ------------------------------------------------------
+ * The temperature-weighted k-NN classifier of Point-MAE_SA3D/main_knn.py:153-198 (knn_classifier) on L2-normalised features, the
+ * solver-free second quality signal beside the linear SVM.  Xn (n,d) f32 training rows, Qn (m,d) f32 test rows, both 16-byte
+ * aligned; the similarity of a pair is their dot product on v_mfma_f32_32x32x2_f32 (exact fp32: one fmaf per column onto the
+ * running sum) in a fixed column order: 16 columns at a time, column 16u + j then column 16u + 8 + j for j = 0..7.  Operands whose
+ * products and partial sums are exactly representable give exact similarities.  The (m,n) similarity matrix is never stored: a
+ * workgroup of 512 threads owns 32 test rows and recomputes their similarities in four 8-bit radix-select passes over the
+ * order-preserving integer keys of the similarities (-0 == +0, NaN above +inf) and one collecting pass.  Selection is exact.
+ * Neighbours are ordered by the strict total order (similarity descending, training row ascending).  Stream-ordered, no host
+ * synchronisation, no global state, no float atomics; every output is bitwise reproducible.
+ * LDS: 98,688 bytes dynamic (survivor keys and rows 2 x 32 x 257 x 4, histogram / class scores 32 x 257 x 4) + 1.5 KiB static;
+ * __launch_bounds__(512); one workgroup per CU.  Measured at 9,843 / 2,468 x 384, 40 classes: 4.3 ms (k = 20), 4.6 ms (k = 200) per
+ * launch; MFMA utilisation and the cost of the LDS atomics: not measured.
+ * Limits (GM3D_EINVAL for n < 1, m < 0, d < 1, k < 1, k > n, ncls < 1, T <= 0 or NaN, a NULL or misaligned required pointer;
+ * GM3D_EUNSUPPORTED beyond the kernel's range; all checked on the host before any launch):
+ *   1 <= n <= 16384, 8 <= d <= 1024, d % 8 == 0, 1 <= k <= min(n, 256), 2 <= ncls <= 64, T > 0, m >= 0.
+ * m == 0 returns GM3D_OK after the shape checks, launching nothing.
+ *
+ * gm3d_knn_probe_normalize: Y[i] = X[i] / max(||X[i]||_2, 1e-12) (F.normalize(p=2, dim=1)), fp32; the row sum of squares is taken by
+ *   one wave, lane l over the columns l, l + 64, ... in order, then a fixed butterfly.  Any n >= 0, d >= 1; Y may be X.
+ * gm3d_knn_probe_neighbours: idx (m,k) int32, sim (m,k) f32 = the k training rows of largest similarity per test row, in the order
+ *   above (sim holds +0 for a similarity of -0).
+ * gm3d_knn_probe_classify: the same selection, then in the same launch: the weight of a neighbour is expf(sim / T) (an fp32
+ *   division, then expf, the reference's div_(T).exp_()); the score of class c is the sum of the weights of the neighbours with
+ *   train_labels[row] == c, added in neighbour-rank order in fp32 (a label outside 0..ncls-1 adds to no class); classes are ranked
+ *   by (score descending, class ascending), so classes without a neighbour rank by id after the voted ones.  top5 (m,5) int64 = the
+ *   first five classes (-1 beyond ncls); probs (m,ncls) f32 = the scores, or NULL; test_labels (m) int64 or NULL: correct[0] += the
+ *   rows whose first class is the label, correct[1] += the rows with the label among the first min(5, k, ncls) classes (int64
+ *   atomics; with test_labels NULL correct is not touched and may be NULL). */
+int gm3d_knn_probe_normalize(const float *X, int n, int d, float *Y, gm3d_stream_t stream);
+int gm3d_knn_probe_neighbours(const float *Xn, const float *Qn, int n, int m, int d, int k, int *idx, float *sim,
+                              gm3d_stream_t stream);
+int gm3d_knn_probe_classify(const float *Xn, const float *Qn, int n, int m, int d, int k, const long long *train_labels, int ncls,
+                            float T, const long long *test_labels, long long *top5, float *probs, long long *correct,
+                            gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
