@@ -151,6 +151,10 @@ SIGNATURES = {
     "gm3d_knn_probe_normalize": [_vp, _i, _i, _vp, _vp],
     "gm3d_knn_probe_neighbours": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
     "gm3d_knn_probe_classify": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "gm3d_gemm_tn_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp],
+    "gm3d_gemm_nt_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i] + [ctypes.c_longlong] * 6 + [_i, _i, _vp],
+    "gm3d_gemm_nt_f32_splits": [_i, _i, _i, _i],
+    "gm3d_gemm_nt_f32_slab_rows": [_i, _i],
 }
 
 

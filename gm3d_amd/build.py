@@ -30,6 +30,7 @@ SOURCES = {
     "gemm_ring.hip": [],
     "gemm_dma.hip": [],
     "gemm_ws.hip": [],
+    "gemm_f32.hip": [],
     "gather.hip": [],
     "attention_masked.hip": [],
     "vote.hip": [],

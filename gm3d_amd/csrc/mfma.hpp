@@ -14,6 +14,9 @@ __device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// exact-fp32 32x32x2 MFMA: lane (c = lane & 31, h = lane >> 5) supplies A[c][h] and B[h][c]; same C/D layout
+__device__ __forceinline__ f32x16 mfma_f32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+
 // C/D layout of a 32x32 MFMA: column = lane & 31, row = crow(reg, lane >> 5).
 __device__ __forceinline__ int crow(int g, int hh) { return (g & 3) + 8 * (g >> 2) + 4 * hh; }
 

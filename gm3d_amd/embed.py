@@ -45,6 +45,8 @@ def splitk_wgrad(dy, x):
     from . import gemm
     if dy.is_contiguous() and x.is_contiguous() and gemm.wgrad_supported(dy.unsqueeze(0), x.unsqueeze(0)):
         return gemm.wgrad_nt(dy.unsqueeze(0), x.unsqueeze(0))[0]      # hand-written NT kernel (row split chosen by shape)
+    if gemm.f32_own(dy) and x.dtype == torch.float32:
+        return gemm.wgrad_nt_f32(dy.unsqueeze(0), x.unsqueeze(0))[0]  # fp32 mode on csrc/gemm_f32.hip (gemm.F32_OWN)
     if (N % 128 and N < 128 and dy.is_contiguous() and x.is_contiguous() and dy.dtype == torch.bfloat16
             and gemm.wgrad_supported(dy.new_empty(1, R, 128), x.unsqueeze(0))):
         # a narrow output (the 96-wide reconstruction head): zero-padded to one 128-column tile for the NT kernel (the library
@@ -132,7 +134,8 @@ class EmbedFn(torch.autograd.Function):
         if pool_fused:      # conv2 + bias + max-pool in one launch: f is written for conv3, (fg, arg1) come from the same tile
             f, fg, arg1 = gemm.linear_pool(a1, W2, _c32(b2), bias_after_pool=False, want_rows=True, group_rows=K)
         else:
-            f = gemm.mm(a1, W2, _c32(b2)) if adt == torch.bfloat16 else torch.addmm(weight_cache.get(b2, adt), a1, W2.t())
+            f = (gemm.mm(a1, W2, _c32(b2)) if (adt == torch.bfloat16 or gemm.f32_own(a1))
+                 else torch.addmm(weight_cache.get(b2, adt), a1, W2.t()))
             fg = torch.empty(BG, C2, dtype=adt, device=dev)
             arg1 = torch.empty(BG, C2, dtype=torch.uint8, device=dev)
             _launch("gm3d_group_max_fwd", {"G": BG, "K": K, "C": C2, "dtype": str(adt)}, lib.gm3d_group_max_fwd, _ptr(f), None,
@@ -192,7 +195,7 @@ class EmbedFn(torch.autograd.Function):
             # conv4 + max-pool + bias: the (rows, 384) product never reaches HBM (the backward needs only arg2)
             _, tok, arg2 = gemm.linear_pool(a2, W4, b4f, bias_after_pool=True, want_rows=False, group_rows=K)
         else:
-            z = gemm.mm(a2, W4) if adt == torch.bfloat16 else a2 @ W4.t()     # groups of k != 32 points (Point-M2AE level 0: k = 16)
+            z = gemm.mm(a2, W4) if (adt == torch.bfloat16 or gemm.f32_own(a2)) else a2 @ W4.t()     # groups of k != 32 points (Point-M2AE level 0: k = 16)
             tok = torch.empty(BGs, C4, dtype=adt, device=dev)
             arg2 = torch.empty(BGs, C4, dtype=torch.uint8, device=dev)
             _launch("gm3d_group_max_fwd", {"G": BGs, "K": K, "C": C4, "dtype": str(adt)}, lib.gm3d_group_max_fwd, _ptr(z),
@@ -262,12 +265,12 @@ class EmbedFn(torch.autograd.Function):
         bf16 = adt == torch.bfloat16 and gemm.ENABLED
         if bf16:            # one transposing launch for both halves: rows [0, C2) of W3^T multiply the per-group term, the rest the rows
             W3T = gemm.transposed(W3)
-        df = gemm.mm(dy, W3T[C2:]) if bf16 else dy @ W3l
+        df = gemm.mm(dy, W3T[C2:]) if bf16 else gemm.mm_nn(dy, W3l) if gemm.f32_own(dy) else dy @ W3l
         dW3l = wgrad(dy, f)
         db3 = colsum(dt, torch.float32)
         dta = dt.to(adt)
         dW3g = wgrad(dta, fg)
-        dfg = gemm.mm(dta, W3T[:C2]) if bf16 else dta @ W3g
+        dfg = gemm.mm(dta, W3T[:C2]) if bf16 else gemm.mm_nn(dta, W3g) if gemm.f32_own(dta) else dta @ W3g
         # max-pool branch joins df; bias grad of conv2
         nrows = lib.gm3d_embed_partial_rows(1, BG, C2)
         part = torch.empty(nrows, C2, dtype=torch.float32, device=dev)

@@ -243,6 +243,8 @@ def _wgrad_batched(dy, x, out=None):
     K = x.shape[2]
     if gemm.wgrad_supported(dy, x) and (out is None or (out.stride(2) == 1 and out.stride(1) == K and out.stride(0) == N * K)):
         return gemm.wgrad_nt(dy, x, out)       # hand-written NT kernel: LDS-DMA staging + transposed LDS reads (csrc/gemm_nt.hip)
+    if gemm.f32_own(dy) and x.dtype == torch.float32:
+        return gemm.wgrad_nt_f32(dy, x, out)   # fp32 mode on our own fp32 MFMA kernel (csrc/gemm_f32.hip): slabs added in slab order
     S = WGRAD_ROW_SPLIT
     if S == 0:      # auto: the smallest split that gives the chip >= 512 output tiles of 128x128 while keeping >= 512 rows each
         S, tiles = 1, nblk * max(N // 128, 1) * max(K // 128, 1)
@@ -503,7 +505,7 @@ class TransformerStackFn(torch.autograd.Function):
                 else:
                     f, g = gemm.linear_gelu(h2, W1, b1, f_out=fo, g_out=GG[i] if need else None)
             else:
-                f = h2 @ W1.t()
+                f = gemm.mm(h2, W1) if gemm.f32_own(h2) else h2 @ W1.t()
                 yield
                 g = bias_gelu_fwd(f, b1, adt, g=GG[i] if need else None)
             yield
@@ -581,17 +583,21 @@ class TransformerStackFn(torch.autograd.Function):
                 df = (gemm.linear_gelu_bwd_dma(d_o, W2T[i], f, b1, DF[i], PGL[i], bm=bm_bwd) if dma_bwd
                       else gemm.linear_gelu_bwd(d_o, W2T[i], f, b1, DF[i], PGL[i]))
             else:
-                dg = d_o @ weight_cache.get(w2, adt)
+                dg = gemm.mm_nn(d_o, weight_cache.get(w2, adt)) if gemm.f32_own(d_o) else d_o @ weight_cache.get(w2, adt)
                 df, _ = bias_gelu_bwd(dg, f, b1, adt, df=DF[i], partial=PGL[i])
             gi[8] = SGL[i]
-            dh2 = gemm.mm(df, W1T[i]) if fuse_mlp_bwd else df @ weight_cache.get(w1, adt)
+            own32 = gemm.f32_own(df)
+            dh2 = (gemm.mm(df, W1T[i]) if fuse_mlp_bwd else gemm.mm_nn(df, weight_cache.get(w1, adt)) if own32
+                   else df @ weight_cache.get(w1, adt))
             dx1, d_p, _ = residual_ln_bwd(dh2, G, x1, m2, r2, ln2w, dp1, T, None, True, adt, R, dy=DP[i],
                                           partial=PLN[2 * i + 1])
             gi[5], gi[6], gi[4] = SLN[2 * i + 1, 0], SLN[2 * i + 1, 1], SLN[2 * i + 1, 2]
             # attention branch: x1 = u + dp1 * (a @ Wproj^T + bproj)
-            da = gemm.mm(d_p, WPT[i]) if fuse_mlp_bwd else d_p @ weight_cache.get(wproj, adt)
+            da = (gemm.mm(d_p, WPT[i]) if fuse_mlp_bwd else gemm.mm_nn(d_p, weight_cache.get(wproj, adt)) if own32
+                  else d_p @ weight_cache.get(wproj, adt))
             dqkv = _attention_bwd(qkv, A[i], da, lse, B, T, H, scale, dqkv=DQ[i])
-            dh1 = gemm.mm(dqkv, WQT[i]) if fuse_mlp_bwd else dqkv @ weight_cache.get(wqkv, adt)
+            dh1 = (gemm.mm(dqkv, WQT[i]) if fuse_mlp_bwd else gemm.mm_nn(dqkv, weight_cache.get(wqkv, adt)) if own32
+                   else dqkv @ weight_cache.get(wqkv, adt))
             last = DIRECT_INPUT_GRADS and i == 0 and nblk > 1 and adt != torch.float32 and ctx.in_dtypes == (adt, adt)
             if last:
                 # the stack's input gradients in the inputs' own (activation) type, written by this last pass instead of two

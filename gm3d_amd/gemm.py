@@ -11,6 +11,84 @@ ENABLED = True            # module attributes below: flipped by the equality tes
 FUSE_GELU = True          # fc1 + bias + GELU as one launch in the fused transformer stack
 FUSE_POOL = True          # mini-PointNet conv + max-pool as one launch
 FUSE_GELU_BWD = True      # fc2 input gradient + GELU backward + fc1 bias-gradient partials
+F32_OWN = False           # fp32 (parity) mode: every dense product on csrc/gemm_f32.hip (exact-fp32 MFMA, fixed accumulation order) instead of
+#                           the BLAS library.  Opt-in; OFF leaves every path what it was
+
+
+def f32_own(x):
+    """does the fp32 product with operand x run on our own fp32 MFMA kernels?"""
+    return F32_OWN and x.is_cuda and x.dtype == torch.float32
+
+
+def _rows_f32(t):
+    """a 2-D fp32 operand the fp32 kernels take as it is: unit inner stride, rows at a non-negative pitch >= the width, 4-byte aligned"""
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t
+
+
+def linear_tn_f32(x, w, bias=None, out=None):
+    """x (M,K) f32, w (N,K) f32, bias (N) f32 or None -> (M,N) f32 = x @ w^T + bias on gm3d_gemm_tn_f32: one MFMA accumulation chain per
+    element whose order depends on K alone (include/gm3d.h).  Row-strided operands (column slices) are taken in place."""
+    x, w = _rows_f32(x), _rows_f32(w)
+    M, K = x.shape
+    N = w.shape[0]
+    assert w.shape[1] == K
+    if bias is not None:
+        bias = bias.detach().float().contiguous()
+    dst = out if (out is not None and out.dtype == torch.float32 and out.stride(1) == 1 and out.stride(0) >= N) else \
+        torch.empty(M, N, dtype=torch.float32, device=x.device)
+    if M > 0:
+        _launch("gm3d_gemm_tn_f32", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_f32, _ptr(x), _ptr(w), _ptr(bias), _ptr(dst), M, N, K,
+                x.stride(0), w.stride(0), dst.stride(0), _stream())
+    if out is not None and dst is not out:
+        out.copy_(dst)
+        return out
+    return dst
+
+
+def nt_f32_splits(nb, R, N, K):
+    return lib.gm3d_gemm_nt_f32_splits(nb, R, N, K)
+
+
+def nt_f32_slab_rows(R, splits):
+    return lib.gm3d_gemm_nt_f32_slab_rows(R, splits)
+
+
+def _batch_f32(t):
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.stride(2) != 1 or t.stride(1) < t.shape[2] or t.stride(0) < 0:
+        t = t.contiguous()
+    return t
+
+
+def wgrad_nt_f32(dy, x, out=None, splits=None, accumulate=False):
+    """out (nb,N,K) f32 (+)= dy[b]^T @ x[b]  (dy (nb,R,N), x (nb,R,K) f32) on gm3d_gemm_nt_f32.  Long R is cut into
+    gm3d_gemm_nt_f32_splits row slabs (a pure function of the shape) that the call adds in ascending slab order: deterministic, no
+    atomics."""
+    dy, x = _batch_f32(dy), _batch_f32(x)
+    nb, R, N = dy.shape
+    K = x.shape[2]
+    assert x.shape[:2] == dy.shape[:2]
+    if splits is None:
+        splits = lib.gm3d_gemm_nt_f32_splits(nb, R, N, K)
+    ok = out is not None and out.dtype == torch.float32 and out.shape == (nb, N, K) and out.stride(2) == 1 and out.stride(1) >= K \
+        and (nb == 1 or out.stride(0) >= (N - 1) * out.stride(1) + K)
+    dst = out if ok else torch.empty(nb, N, K, dtype=torch.float32, device=dy.device)
+    if accumulate and not ok:
+        assert out is not None
+        dst.copy_(out)
+    part = torch.empty(nb, splits, N, K, dtype=torch.float32, device=dy.device) if splits > 1 else None
+    _launch("gm3d_gemm_nt_f32", {"B": nb, "M": R, "N": N, "K": K, "splits": splits}, lib.gm3d_gemm_nt_f32, _ptr(dy), _ptr(x), _ptr(dst),
+            _ptr(part), nb, R, N, K, dy.stride(1), x.stride(1), dst.stride(1), dy.stride(0), x.stride(0), dst.stride(0), int(splits),
+            int(bool(accumulate)), _stream())
+    if out is not None and dst is not out:
+        out.copy_(dst)
+        return out
+    return dst
 
 
 def supported(x, w):
@@ -301,6 +379,8 @@ def mm(x, w, bias=None, out=None):
     if how.startswith("dma"):
         bm, bn = how[3:].split("x")
         return linear_tn_dmaw(x, w, bias, out, bm=int(bm), bn=int(bn))
+    if f32_own(x) and w.dtype == torch.float32 and x.dim() == 2 and w.dim() == 2:
+        return linear_tn_f32(x, w, bias, out)
     y = x @ w.t()
     if bias is not None:
         y = y + bias.to(y.dtype)
@@ -371,6 +451,8 @@ def mm_nn(x, w, out=None):
         wt = _transposed_for_mm_nn(w)
         if supported(x, wt) or ragged_supported(x, wt):
             return mm(x, wt, None, out)
+    if f32_own(x) and w.dtype == torch.float32 and x.dim() == 2 and w.dim() == 2:
+        return linear_tn_f32(x, transposed(w), None, out)       # the TN kernel on the transposed weight (a copy, no product)
     y = x @ w
     return y if out is None else out.copy_(y)
 

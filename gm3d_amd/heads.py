@@ -60,6 +60,8 @@ class LinearBiasFn(torch.autograd.Function):
                 y = gemm.mm(x2, W, _c32(b) if b is not None else None)
             elif _ragged_ok(x2, W):
                 y = gemm.linear_tn_ring(x2, W, _c32(b) if b is not None else None)
+            elif gemm.f32_own(x2):
+                y = gemm.mm(x2, W, _c32(b) if b is not None else None)      # fp32 mode on csrc/gemm_f32.hip (gemm.F32_OWN)
             else:
                 y = torch.addmm(weight_cache.get(b, adt), x2, W.t()) if b is not None else x2 @ W.t()
             ctx.save_for_backward(x2, w)

@@ -124,4 +124,12 @@ class PointTransformer(nn.Module):
         return torch.cat([x[:, 0], x[:, 1:].max(1)[0]], dim=-1)
 
     def forward(self, pts):
-        return self.cls_head_finetune(self.forward_features(pts))
+        x = self.forward_features(pts)
+        from . import gemm, heads
+        if gemm.f32_own(x) and heads._adt() == torch.float32:
+            # fp32 mode on our own kernels (gemm.F32_OWN): the head's three Linear layers through heads.LinearBiasFn -- forward, input
+            # and weight gradients on csrc/gemm_f32.hip, bias gradients by our column sums -- instead of nn.Linear's library products
+            for m in self.cls_head_finetune:
+                x = heads.LinearBiasFn.apply(x, m.weight, m.bias, torch.float32) if isinstance(m, nn.Linear) else m(x)
+            return x
+        return self.cls_head_finetune(x)

@@ -567,6 +567,32 @@ int gm3d_gemm_nt_tiles(int N, int K);
 int gm3d_gemm_nt_bf16_multi(int count, const void *const *dY, const void *const *X, float *const *out, float *const *part, const int *batch,
                             const int *R, const int *N, const int *K, const int *ldy, const int *ldx, const long long *stride_y,
                             const long long *stride_x, const long long *stride_o, const int *splits, gm3d_stream_t stream);
+/* fp32 GEMMs of the parity mode on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32, fp32 accumulate): csrc/gemm_f32.hip.
+ * ACCUMULATION-ORDER RULE (both kernels): every output element is one chain of MFMA accumulations over the reduction index whose
+ * order depends on the reduction length alone -- units of 16 indices in ascending order; inside unit u, step j = 0..7 adds the
+ * products at 16u + j and 16u + 8 + j (TN: k; NT: rows 16u + 2j and 16u + 2j + 1).  Neither the other two sizes, the tile height,
+ * the grid nor the CU that ran a tile enters; no split-K in TN, no atomics anywhere: equal inputs give equal bits, and a row of a
+ * TN product has the bits it would have in a product with more or fewer rows.
+ *
+ * gm3d_gemm_tn_f32: C (M,N) = A (M,K) . W (N,K)^T (+ bias (N), NULL = none); all fp32, row-major with row pitches lda / ldw / ldc
+ * in elements.  M, N, K >= 1, ragged in all three (K = 3 works); rows need 4-byte alignment only (16-byte loads are taken when a
+ * pointer and its pitch allow).  Elements of C outside the (M,N) window are not touched.  M, N or K < 1, a NULL operand, or a
+ * pitch smaller than the width (negative ones included): GM3D_EINVAL; a misaligned pointer or more than 2^31 tiles:
+ * GM3D_EUNSUPPORTED -- checked on the host before any launch. */
+int gm3d_gemm_tn_f32(const float *A, const float *W, const float *bias, float *C, int M, int N, int K, long long lda,
+                     long long ldw, long long ldc, gm3d_stream_t stream);
+/* gm3d_gemm_nt_f32: out[b] (N,K) = sum over r of dY[b] (R,N)^T . X[b] (R,K), b < batch (the weight gradient); row pitches ldy /
+ * ldx / ldo and batch strides in elements; accumulate != 0 adds the product to what out holds.  splits > 1 cuts the rows into
+ * slabs of gm3d_gemm_nt_f32_slab_rows(R, splits) rows (a multiple of 32; the last one shorter, none empty, splits <= 64): each slab
+ * is a chain of its own, as if computed by a splits = 1 call on its rows, written to part (batch, splits, N, K) f32, and a second
+ * launch inside the call adds the slabs in ascending slab order (then adds out when accumulate).  gm3d_gemm_nt_f32_splits is the
+ * split the package uses: a pure function of (batch, R, N, K).  Errors as for gm3d_gemm_tn_f32; an empty slab or splits > 1 without
+ * part: GM3D_EINVAL. */
+int gm3d_gemm_nt_f32(const float *dY, const float *X, float *out, float *part, int batch, int R, int N, int K, long long ldy,
+                     long long ldx, long long ldo, long long stride_y, long long stride_x, long long stride_o, int splits,
+                     int accumulate, gm3d_stream_t stream);
+int gm3d_gemm_nt_f32_splits(int batch, int R, int N, int K);
+int gm3d_gemm_nt_f32_slab_rows(int R, int splits);
 /* Masked multi-head attention of the hierarchical (Point-M2AE) encoder blocks -- SURVEY.md 8f.4; the reference ships only the
  * hyper-parameters (Point-M2AE_SA3D/cfgs/config_Point_M2AE.yaml:57-99: dims 96/192/384, 6 heads, local_radius 0.32/0.64/1.28).
  * qkv (B,T,3,H,HD) as the qkv Linear emits it, HD in {16,32,64}, T <= 512; mask (B,T,ceil(T/32)) uint32 bitset, bit (j&31) of
