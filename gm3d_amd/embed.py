@@ -18,8 +18,6 @@ from .fused import weight_cache, LNC  # noqa: F401
 from . import gemm
 from .ops import _launch, _ptr, _stream, _DT
 
-SPLITK = 64  # row chunks of the weight-gradient GEMMs (K = 262,144 rows would otherwise run on a handful of CUs)
-
 
 def _finish(partial, nrows, ncols, pitch=None):
     out = torch.empty(ncols, dtype=torch.float32, device=partial.device)
@@ -39,39 +37,16 @@ def colsum(m, adt):
 
 
 def splitk_wgrad(dy, x):
-    """dW (N,K) f32 = dy (R,N)^T @ x (R,K) with R split into SPLITK batched chunks + a deterministic sum."""
-    R, N = dy.shape
-    K = x.shape[1]
-    from . import gemm
-    if dy.is_contiguous() and x.is_contiguous() and gemm.wgrad_supported(dy.unsqueeze(0), x.unsqueeze(0)):
-        return gemm.wgrad_nt(dy.unsqueeze(0), x.unsqueeze(0))[0]      # hand-written NT kernel (row split chosen by shape)
-    if gemm.f32_own(dy) and x.dtype == torch.float32:
-        return gemm.wgrad_nt_f32(dy.unsqueeze(0), x.unsqueeze(0))[0]  # fp32 mode on csrc/gemm_f32.hip (gemm.F32_OWN)
-    if (N % 128 and N < 128 and dy.is_contiguous() and x.is_contiguous() and dy.dtype == torch.bfloat16
-            and gemm.wgrad_supported(dy.new_empty(1, R, 128), x.unsqueeze(0))):
-        # a narrow output (the 96-wide reconstruction head): zero-padded to one 128-column tile for the NT kernel (the library
-        # runs this shape on 32x32 tiles: 88 us per step)
-        pad = torch.zeros(R, 128, dtype=dy.dtype, device=dy.device)
-        pad[:, :N] = dy
-        return gemm.wgrad_nt(pad.unsqueeze(0), x.unsqueeze(0))[0][:N].contiguous()
-    S = SPLITK if R % SPLITK == 0 and R >= 64 * SPLITK else 1
-    a = dy.view(S, R // S, N).transpose(1, 2)
-    b = x.view(S, R // S, K)
-    if dy.dtype == torch.float32:
-        part = torch.bmm(a, b)
-    else:
-        try:
-            part = torch.bmm(a, b, out_dtype=torch.float32)
-        except TypeError:
-            part = torch.bmm(a, b).float()
-    if S == 1:
-        return part[0]
-    from . import fused
-    if not fused.SUM_FEW_ROWS:
-        return _finish(part.view(S, N * K), S, N * K).view(N, K)
-    out = torch.empty(N, K, dtype=torch.float32, device=dy.device)
-    _launch("gm3d_sum_few_rows", {"rows": S, "cols": N * K}, lib.gm3d_sum_few_rows, _ptr(part), 1, S, N * K, _ptr(out), _stream())
-    return out
+    """dW (N,K) f32 = dy (R,N)^T @ x (R,K): gemm.wgrad's 2-D form."""
+    return gemm.wgrad(dy, x)
+
+
+def linear_bias(x, W, b, adt):
+    """x @ W^T + b for a layer that always has a bias: in the epilogue of the kernel gemm.mm runs; where that is the library, in the
+    library's own fused form (addmm: not the bits of the product followed by an addition, which is what mm does there)."""
+    if gemm.route(x, W)[0] != "lib":
+        return gemm.mm(x, W, _c32(b))
+    return torch.addmm(weight_cache.get(b, adt), x, W.t())
 
 
 def _c32(p):
@@ -134,8 +109,7 @@ class EmbedFn(torch.autograd.Function):
         if pool_fused:      # conv2 + bias + max-pool in one launch: f is written for conv3, (fg, arg1) come from the same tile
             f, fg, arg1 = gemm.linear_pool(a1, W2, _c32(b2), bias_after_pool=False, want_rows=True, group_rows=K)
         else:
-            f = (gemm.mm(a1, W2, _c32(b2)) if (adt == torch.bfloat16 or gemm.f32_own(a1))
-                 else torch.addmm(weight_cache.get(b2, adt), a1, W2.t()))
+            f = linear_bias(a1, W2, b2, adt)
             fg = torch.empty(BG, C2, dtype=adt, device=dev)
             arg1 = torch.empty(BG, C2, dtype=torch.uint8, device=dev)
             _launch("gm3d_group_max_fwd", {"G": BG, "K": K, "C": C2, "dtype": str(adt)}, lib.gm3d_group_max_fwd, _ptr(f), None,
@@ -195,7 +169,7 @@ class EmbedFn(torch.autograd.Function):
             # conv4 + max-pool + bias: the (rows, 384) product never reaches HBM (the backward needs only arg2)
             _, tok, arg2 = gemm.linear_pool(a2, W4, b4f, bias_after_pool=True, want_rows=False, group_rows=K)
         else:
-            z = gemm.mm(a2, W4) if (adt == torch.bfloat16 or gemm.f32_own(a2)) else a2 @ W4.t()     # groups of k != 32 points (Point-M2AE level 0: k = 16)
+            z = gemm.mm(a2, W4)     # groups of k != 32 points (Point-M2AE level 0: k = 16)
             tok = torch.empty(BGs, C4, dtype=adt, device=dev)
             arg2 = torch.empty(BGs, C4, dtype=torch.uint8, device=dev)
             _launch("gm3d_group_max_fwd", {"G": BGs, "K": K, "C": C4, "dtype": str(adt)}, lib.gm3d_group_max_fwd, _ptr(z),
@@ -243,7 +217,7 @@ class EmbedFn(torch.autograd.Function):
                 out = torch.empty(1, dy_.shape[1], x_.shape[1], dtype=torch.float32, device=dev)
                 later.append((dy_.unsqueeze(0), x_.unsqueeze(0), out))
                 return out[0]
-            return splitk_wgrad(dy_, x_)
+            return gemm.wgrad(dy_, x_)
         dW4 = wgrad(dz, a2)
         # BN2 + ReLU: the sums run over the rows that carry a gradient, dy is written for every row
         nrows = lib.gm3d_embed_partial_rows(1, BGs, C3)
@@ -265,12 +239,12 @@ class EmbedFn(torch.autograd.Function):
         bf16 = adt == torch.bfloat16 and gemm.ENABLED
         if bf16:            # one transposing launch for both halves: rows [0, C2) of W3^T multiply the per-group term, the rest the rows
             W3T = gemm.transposed(W3)
-        df = gemm.mm(dy, W3T[C2:]) if bf16 else gemm.mm_nn(dy, W3l) if gemm.f32_own(dy) else dy @ W3l
+        df = gemm.mm(dy, W3T[C2:]) if bf16 else gemm.mm_nn(dy, W3l)
         dW3l = wgrad(dy, f)
         db3 = colsum(dt, torch.float32)
         dta = dt.to(adt)
         dW3g = wgrad(dta, fg)
-        dfg = gemm.mm(dta, W3T[:C2]) if bf16 else gemm.mm_nn(dta, W3g) if gemm.f32_own(dta) else dta @ W3g
+        dfg = gemm.mm(dta, W3T[:C2]) if bf16 else gemm.mm_nn(dta, W3g)
         # max-pool branch joins df; bias grad of conv2
         nrows = lib.gm3d_embed_partial_rows(1, BG, C2)
         part = torch.empty(nrows, C2, dtype=torch.float32, device=dev)

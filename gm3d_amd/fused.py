@@ -234,62 +234,6 @@ def _attention_bwd(qkv, out, dout, lse, B, T, H, scale, dqkv=None):
     return dqkv
 
 
-def _wgrad_batched(dy, x, out=None):
-    """dW[i] = dy[i]^T @ x[i] for every block of a stack in ONE batched GEMM, fp32 result.
-    out (nblk,N,K) f32 (optional): the destination -- the parameters' slots in the optimizer's flat gradient buffer.
-    (K = rows is 3200..8192 and the output is only 384..1536 wide: a single such GEMM fills a fraction of the
-    256 CUs -- 50 us each through hipBLASLt -- while the batch over blocks runs at ~16 us per block.)"""
-    nblk, R, N = dy.shape
-    K = x.shape[2]
-    if gemm.wgrad_supported(dy, x) and (out is None or (out.stride(2) == 1 and out.stride(1) == K and out.stride(0) == N * K)):
-        return gemm.wgrad_nt(dy, x, out)       # hand-written NT kernel: LDS-DMA staging + transposed LDS reads (csrc/gemm_nt.hip)
-    if gemm.f32_own(dy) and x.dtype == torch.float32:
-        return gemm.wgrad_nt_f32(dy, x, out)   # fp32 mode on our own fp32 MFMA kernel (csrc/gemm_f32.hip): slabs added in slab order
-    S = WGRAD_ROW_SPLIT
-    if S == 0:      # auto: the smallest split that gives the chip >= 512 output tiles of 128x128 while keeping >= 512 rows each
-        S, tiles = 1, nblk * max(N // 128, 1) * max(K // 128, 1)
-        while tiles * S < 512 and S < 8 and R % (2 * S) == 0 and R // (2 * S) >= 512:
-            S *= 2
-    elif nblk > 4 or R // S < 1024:
-        S = 1
-    if S > 1 and R % S == 0 and dy.is_contiguous() and x.is_contiguous():
-        # few blocks (the 4-block decoders): nblk * (N/128) * (K/128) tiles do not fill 256 CUs and each runs an 8192-deep
-        # reduction -- split the rows S ways into more batches and add the S partial products with the two-stage sum
-        part = _wgrad_batched_plain(dy.view(nblk * S, R // S, N), x.view(nblk * S, R // S, K))
-        if out is None:
-            out = torch.empty(nblk, N, K, dtype=torch.float32, device=dy.device)
-        if SUM_FEW_ROWS:
-            _launch("gm3d_sum_few_rows", {"rows": nblk * S, "cols": N * K}, lib.gm3d_sum_few_rows, _ptr(part), nblk, S, N * K,
-                    _ptr(out), _stream())
-        else:
-            _launch("gm3d_colsum_finish_batched", {"rows": nblk * S, "cols": N * K}, lib.gm3d_colsum_finish_batched, _ptr(part), nblk,
-                    S * N * K, S, N * K, N * K, _ptr(out), N * K, _stream())
-        return out
-    return _wgrad_batched_plain(dy, x, out)
-
-
-SUM_FEW_ROWS = True
-WGRAD_ROW_SPLIT = 4      # library fallback only (shapes the NT kernel does not take): 0 = auto, 1 = off, n = n-way for <=4-block stacks
-
-
-_BMM_OUT_OK = [True]     # torch.bmm(..., out_dtype=, out=) available?
-
-
-def _wgrad_batched_plain(dy, x, out=None):
-    if dy.dtype == torch.float32:
-        return torch.bmm(dy.transpose(1, 2), x) if out is None else torch.bmm(dy.transpose(1, 2), x, out=out)
-    if out is not None and _BMM_OUT_OK[0]:
-        try:
-            return torch.bmm(dy.transpose(1, 2), x, out_dtype=torch.float32, out=out)
-        except (TypeError, RuntimeError):
-            _BMM_OUT_OK[0] = False
-    try:
-        r = torch.bmm(dy.transpose(1, 2), x, out_dtype=torch.float32)
-    except TypeError:
-        r = torch.bmm(dy.transpose(1, 2), x).float()
-    return r if out is None else out.copy_(r)
-
-
 WGRAD_MIN_BLOCKS = 5      # stacks with fewer blocks (the 4-block decoders) DEFER their weight-gradient GEMMs to the deep stack's fork point
 _ASYNC_WGRAD = {"stream": None, "used": False, "min_blocks": 5, "deferred": []}
 
@@ -304,9 +248,9 @@ def _wgrad_many(reqs):
         per = -(-len(reqs) // -(-len(reqs) // 16))
         for i in range(0, len(reqs), per):
             chunk = reqs[i:i + per]
-            res += gemm.wgrad_nt_multi(chunk) if len(chunk) > 1 else [_wgrad_batched(*chunk[0])]
+            res += gemm.wgrad_nt_multi(chunk) if len(chunk) > 1 else [gemm.wgrad(*chunk[0])]
         return res
-    return [_wgrad_batched(dy, x, out) for dy, x, out in reqs]
+    return [gemm.wgrad(dy, x, out) for dy, x, out in reqs]
 
 
 def defer_wgrad(dy, x, w=None):
@@ -325,8 +269,7 @@ def defer_wgrad(dy, x, w=None):
             if gemm.wgrad_multi_ok(dy.unsqueeze(0), x.unsqueeze(0), out):
                 reg["deferred"].append(((dy, x), [(dy.unsqueeze(0), x.unsqueeze(0), out)]))
                 return out[0]
-    from .embed import splitk_wgrad
-    return splitk_wgrad(dy, x)
+    return gemm.wgrad(dy, x)
 
 
 DEFER_HEAD_WGRAD = False  # the heads' / positional MLP's weight gradients inside the stacks' one-launch form (fused.defer_wgrad): measured
@@ -396,11 +339,6 @@ def block_params(block):
             block.mlp.fc2.bias]
 
 
-def _mm(x, w):
-    """x (R,K) @ w (N,K)^T on the kernel gemm.choose names for the shape (hand-written register-prefetch / LDS-DMA ring / library)."""
-    return gemm.mm(x, w)
-
-
 class TransformerStackFn(torch.autograd.Function):
     """args: x (B,T,C), pos (B,T,C), meta, final_w, final_b, then PER_BLOCK tensors per block.
     meta: dict(num_heads, scale, eps, final_eps, adt, dp=[(scale_attn|None, scale_mlp|None) per block])."""
@@ -458,7 +396,7 @@ class TransformerStackFn(torch.autograd.Function):
                 if i == 0:
                     u, h1, m1, r1 = residual_ln_fwd(res, y, bias, rs, T, posa, ln1w, ln1b, eps, adt, R, h=H1[i] if need else None)
                     yield
-                    qkv = _mm(h1, weight_cache.get(wqkv, adt))
+                    qkv = gemm.mm(h1, weight_cache.get(wqkv, adt))
                 else:       # u, st1: the previous block's fc2 epilogue
                     qkv, m1, r1 = gemm.linear_lna(u16, st1, ln1w, ln1b, eps, weight_cache.get(wqkv, adt), None,
                                                   h_out=H1[i] if need else None, want_stats=need)
@@ -477,7 +415,7 @@ class TransformerStackFn(torch.autograd.Function):
                 if i + 1 < nblk:
                     u, u16, st1 = gemm.linear_res(g, weight_cache.get(w2, adt), b2, x1, dp2, T, posa)
                 else:
-                    o = _mm(g, weight_cache.get(w2, adt))
+                    o = gemm.mm(g, weight_cache.get(w2, adt))
                     res, y, bias, rs = x1, o, b2, dp2
                 yield
                 continue
@@ -488,11 +426,11 @@ class TransformerStackFn(torch.autograd.Function):
                 # q|k|v never leave the CU in the no-grad (teacher) pass; with a backward to come they are written on the side
                 a, lse, qkv = _attention_qkv_fwd(h1, Wq, B, T, H, scale, out=A[i] if need else None, want_qkv=need, want_lse=need)
             else:
-                qkv = _mm(h1, Wq)
+                qkv = gemm.mm(h1, Wq)
                 yield
                 a, lse = _attention_fwd(qkv, B, T, H, scale, out=A[i] if need else None)
             yield
-            p = _mm(a, weight_cache.get(wproj, adt))
+            p = gemm.mm(a, weight_cache.get(wproj, adt))
             yield
             x1, h2, m2, r2 = residual_ln_fwd(u, p, bproj, dp1, T, None, ln2w, ln2b, eps, adt, R, h=H2[i] if need else None)
             yield
@@ -505,11 +443,11 @@ class TransformerStackFn(torch.autograd.Function):
                 else:
                     f, g = gemm.linear_gelu(h2, W1, b1, f_out=fo, g_out=GG[i] if need else None)
             else:
-                f = gemm.mm(h2, W1) if gemm.f32_own(h2) else h2 @ W1.t()
+                f = gemm.mm(h2, W1)
                 yield
                 g = bias_gelu_fwd(f, b1, adt, g=GG[i] if need else None)
             yield
-            o = _mm(g, weight_cache.get(w2, adt))
+            o = gemm.mm(g, weight_cache.get(w2, adt))
             yield
             if need:
                 saved += [u, m1, r1, qkv, lse, x1, m2, r2, f]
@@ -583,21 +521,17 @@ class TransformerStackFn(torch.autograd.Function):
                 df = (gemm.linear_gelu_bwd_dma(d_o, W2T[i], f, b1, DF[i], PGL[i], bm=bm_bwd) if dma_bwd
                       else gemm.linear_gelu_bwd(d_o, W2T[i], f, b1, DF[i], PGL[i]))
             else:
-                dg = gemm.mm_nn(d_o, weight_cache.get(w2, adt)) if gemm.f32_own(d_o) else d_o @ weight_cache.get(w2, adt)
+                dg = gemm.mm_nn(d_o, weight_cache.get(w2, adt))
                 df, _ = bias_gelu_bwd(dg, f, b1, adt, df=DF[i], partial=PGL[i])
             gi[8] = SGL[i]
-            own32 = gemm.f32_own(df)
-            dh2 = (gemm.mm(df, W1T[i]) if fuse_mlp_bwd else gemm.mm_nn(df, weight_cache.get(w1, adt)) if own32
-                   else df @ weight_cache.get(w1, adt))
+            dh2 = gemm.mm(df, W1T[i]) if fuse_mlp_bwd else gemm.mm_nn(df, weight_cache.get(w1, adt))
             dx1, d_p, _ = residual_ln_bwd(dh2, G, x1, m2, r2, ln2w, dp1, T, None, True, adt, R, dy=DP[i],
                                           partial=PLN[2 * i + 1])
             gi[5], gi[6], gi[4] = SLN[2 * i + 1, 0], SLN[2 * i + 1, 1], SLN[2 * i + 1, 2]
             # attention branch: x1 = u + dp1 * (a @ Wproj^T + bproj)
-            da = (gemm.mm(d_p, WPT[i]) if fuse_mlp_bwd else gemm.mm_nn(d_p, weight_cache.get(wproj, adt)) if own32
-                  else d_p @ weight_cache.get(wproj, adt))
+            da = gemm.mm(d_p, WPT[i]) if fuse_mlp_bwd else gemm.mm_nn(d_p, weight_cache.get(wproj, adt))
             dqkv = _attention_bwd(qkv, A[i], da, lse, B, T, H, scale, dqkv=DQ[i])
-            dh1 = (gemm.mm(dqkv, WQT[i]) if fuse_mlp_bwd else gemm.mm_nn(dqkv, weight_cache.get(wqkv, adt)) if own32
-                   else dqkv @ weight_cache.get(wqkv, adt))
+            dh1 = gemm.mm(dqkv, WQT[i]) if fuse_mlp_bwd else gemm.mm_nn(dqkv, weight_cache.get(wqkv, adt))
             last = DIRECT_INPUT_GRADS and i == 0 and nblk > 1 and adt != torch.float32 and ctx.in_dtypes == (adt, adt)
             if last:
                 # the stack's input gradients in the inputs' own (activation) type, written by this last pass instead of two

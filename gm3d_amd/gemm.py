@@ -1,6 +1,18 @@
-"""bf16 GEMM of the block / mini-PointNet shapes on the hand-written MFMA kernel (csrc/gemm.hip): y = x @ w^T (+ bias), and
-its fused-epilogue forms (fc1+GELU, fc2-dgrad+GELU', conv+max-pool).  DESIGN.md 3b' has the design and the measurements;
-`choose` names the kernel for every plain shape (table: tools/gemm_kbench.py -> profiles/r02_gemm_kbench.txt)."""
+"""Every dense product of the package, and the one place that decides what runs it.
+
+    mm(x, w, bias, out)    x (M,K) @ w (N,K)^T (+ bias)   `route` names the target, `_tn` launches it
+    mm_nn(x, w, out)       x (M,N) @ w (N,K): a layer's input gradient, the TN product against a transposed copy of w
+    wgrad(dy, x, out)      dy^T @ x in fp32: a layer's (2-D) or a whole stack's (batched) weight gradient
+
+bf16 operands in the kernels' layout (`_rows_ok`) run on the hand-written MFMA kernels: csrc/gemm.hip (register prefetch, ragged
+widths), gemm_ring.hip (LDS-DMA ring), gemm_dma.hip (LDS-DMA double buffer, bm x bn tiles), gemm_ws.hip (weight-stationary, tall
+products), gemm_nt.hip (weight gradients); `choose` is the per-shape table (tools/gemm_kbench.py -> profiles/r03_gemm_kbench.txt).
+fp32 operands run on csrc/gemm_f32.hip under F32_OWN and on the BLAS library otherwise; the library is also where bf16 operands
+outside the layout rules end (never on the bf16 step's path: tools/leftover_sites.py lists none).  The fused-epilogue forms (fc1 +
+GELU, fc2-dgrad + GELU', conv + max-pool, LayerNorm / BatchNorm epilogues) are entry points of their own below; their callers
+pick them by the same predicates.  DESIGN.md 3b' has the design and the measurements."""
+import ctypes
+
 import torch
 
 from ._capi import lib
@@ -18,6 +30,11 @@ F32_OWN = False           # fp32 (parity) mode: every dense product on csrc/gemm
 def f32_own(x):
     """does the fp32 product with operand x run on our own fp32 MFMA kernels?"""
     return F32_OWN and x.is_cuda and x.dtype == torch.float32
+
+
+def _f32_pair(x, w):
+    """two fp32 matrices whose product runs on csrc/gemm_f32.hip"""
+    return f32_own(x) and w.dtype == torch.float32 and x.dim() == 2 and w.dim() == 2
 
 
 def _rows_f32(t):
@@ -91,12 +108,16 @@ def wgrad_nt_f32(dy, x, out=None, splits=None, accumulate=False):
     return dst
 
 
+def _rows_ok(t, mult=1, dim=2):
+    """the operand layout every bf16 MFMA kernel here reads in place: on the device, bf16, `dim`-D, unit inner stride, rows at a pitch
+    that is a multiple of 8 and >= the width, 16-byte aligned base; the width a multiple of `mult`"""
+    return (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == dim and t.shape[-1] % mult == 0 and t.stride(-1) == 1
+            and t.stride(-2) % 8 == 0 and t.stride(-2) >= t.shape[-1] and t.data_ptr() % 16 == 0)
+
+
 def supported(x, w):
-    """x (M,K) bf16 with unit inner stride, w (N,K) bf16 contiguous rows; N % 128 == 0, K % 64 == 0."""
-    return (ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.dim() == 2 and w.dim() == 2
-            and x.shape[1] == w.shape[1] and w.shape[0] % 128 == 0 and w.shape[1] % 64 == 0 and x.stride(1) == 1
-            and w.stride(1) == 1 and x.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1] and w.stride(0) >= w.shape[1]
-            and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
+    """x (M,K), w (N,K) bf16 rows (_rows_ok); N % 128 == 0, K % 64 == 0."""
+    return ENABLED and _rows_ok(x, 64) and _rows_ok(w, 64) and x.shape[1] == w.shape[1] and w.shape[0] % 128 == 0
 
 
 RAGGED = True            # widths that are multiples of 8 but not of the tiles (Point-M2AE's 96 / 192 / 288 / 576) on our own kernels
@@ -104,45 +125,35 @@ RAGGED = True            # widths that are multiples of 8 but not of the tiles (
 
 def ragged_supported(x, w):
     """the plain product on csrc/gemm.hip's ragged form: N, K any multiples of 8 (W rows past N clamped, the last K-stage zero-filled)."""
-    return (ENABLED and RAGGED and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.dim() == 2 and w.dim() == 2
-            and x.shape[1] == w.shape[1] and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0 and w.shape[1] >= 8 and x.stride(1) == 1
-            and w.stride(1) == 1 and x.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1] and w.stride(0) >= w.shape[1]
-            and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0)
+    return (ENABLED and RAGGED and _rows_ok(x, 8) and _rows_ok(w, 8) and x.shape[1] == w.shape[1] and w.shape[0] % 8 == 0
+            and w.shape[1] >= 8)
+
+
+def _tn(sym, x, w, bias, outs, *tail):
+    """ONE launch of the TN kernel `sym`: x (M,K), w (N,K) bf16, bias (N) f32 | None -> outs, a tuple of (M,N) bf16 destinations (None:
+    not wanted; the last is made here when None), behind the common argument list the kernel's own integers `tail` (bm / bn)."""
+    M, K = x.shape
+    N = w.shape[0]
+    if outs[-1] is None:
+        outs = outs[:-1] + (torch.empty(M, N, dtype=torch.bfloat16, device=x.device),)
+    _launch(sym, {"M": M, "N": N, "K": K}, getattr(lib, sym), _ptr(x), _ptr(w), _ptr(bias), *[_ptr(o) for o in outs], M, N, K, x.stride(0),
+            w.stride(0), *[o.stride(0) if o is not None else 0 for o in outs], *[int(t) for t in tail], _stream())
+    return outs
 
 
 def linear_tn(x, w, bias=None, out=None):
     """x (M,K) bf16, w (N,K) bf16, bias (N) f32 or None -> (M,N) bf16 = x @ w^T + bias (fp32 accumulate, one rounding)."""
-    M, K = x.shape
-    N = w.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-    _launch("gm3d_gemm_tn_bf16", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), M, N, K,
-            x.stride(0), w.stride(0), out.stride(0), _stream())
-    return out
+    return _tn("gm3d_gemm_tn_bf16", x, w, bias, (out,))[0]
 
 
 def linear_tn_ring(x, w, bias=None, out=None, bm=None):
     """linear_tn through the LDS-DMA ring kernel (csrc/gemm_ring.hip): same results bit for bit; for long K over few tiles."""
-    M, K = x.shape
-    N = w.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-    if bm is None:
-        bm = 64 if M <= 4096 else 128
-    _launch("gm3d_gemm_tn_bf16_ring", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_ring, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), M, N,
-            K, x.stride(0), w.stride(0), out.stride(0), int(bm), _stream())
-    return out
+    return _tn("gm3d_gemm_tn_bf16_ring", x, w, bias, (out,), dma_bm(x.shape[0]) if bm is None else bm)[0]
 
 
 def linear_tn_ring96(x, w, bias=None, out=None, bm=64):
     """linear_tn through the ring kernel with 96-column tiles (N % 96 == 0; csrc/gemm_ring.hip): bit-identical."""
-    M, K = x.shape
-    N = w.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-    _launch("gm3d_gemm_tn_bf16_ring96", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_ring96, _ptr(x), _ptr(w), _ptr(bias), _ptr(out),
-            M, N, K, x.stride(0), w.stride(0), out.stride(0), int(bm), _stream())
-    return out
+    return _tn("gm3d_gemm_tn_bf16_ring96", x, w, bias, (out,), bm)[0]
 
 
 USE_DMA = True            # K = 384 products over >= 6 column tiles of 192 on csrc/gemm_dma.hip (qkv, fc1 + GELU, fc2 input gradient)
@@ -154,30 +165,17 @@ def dma_bm(M):
 
 
 def dma_supported(x, w):
-    return USE_DMA and supported(x, w) and w.shape[0] % 192 == 0 and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
+    return USE_DMA and supported(x, w) and w.shape[0] % 192 == 0
 
 
 def linear_tn_dma(x, w, bias=None, out=None, bm=64):
     """linear_tn through the 192-column LDS-DMA double-buffer kernel (csrc/gemm_dma.hip): same results bit for bit; for K = 384."""
-    M, K = x.shape
-    N = w.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-    _launch("gm3d_gemm_tn_bf16_dma", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_dma, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), M, N,
-            K, x.stride(0), w.stride(0), out.stride(0), int(bm), _stream())
-    return out
+    return _tn("gm3d_gemm_tn_bf16_dma", x, w, bias, (out,), bm)[0]
 
 
 def linear_gelu_dma(x, w, bias, f_out=None, g_out=None, bm=64):
     """linear_gelu on csrc/gemm_dma.hip (bit-identical)."""
-    M, K = x.shape
-    N = w.shape[0]
-    if g_out is None:
-        g_out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-    _launch("gm3d_gemm_tn_bf16_dma_gelu", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_dma_gelu, _ptr(x), _ptr(w), _ptr(bias),
-            _ptr(f_out), _ptr(g_out), M, N, K, x.stride(0), w.stride(0), f_out.stride(0) if f_out is not None else 0,
-            g_out.stride(0), int(bm), _stream())
-    return f_out, g_out
+    return _tn("gm3d_gemm_tn_bf16_dma_gelu", x, w, bias, (f_out, g_out), bm)
 
 
 # LayerNorm folded into the producer / consumer GEMMs (fused.py).  OFF: measured on MI355X at B = 128 (same-box A/B, round 2) the
@@ -230,14 +228,7 @@ def linear_lna(U, stats, gamma, beta, eps, w, bias=None, gelu=False, f_out=None,
 def linear_gelu(x, w, bias, f_out=None, g_out=None):
     """fc1 -> GELU with the activation in the GEMM epilogue: g = GELU(x @ w^T + bias); `f_out` (optional) receives the
     bf16 pre-activation WITHOUT bias (what bias_gelu_bwd re-reads).  -> (f_out | None, g)."""
-    M, K = x.shape
-    N = w.shape[0]
-    if g_out is None:
-        g_out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-    _launch("gm3d_gemm_tn_bf16_gelu", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_gelu, _ptr(x), _ptr(w), _ptr(bias),
-            _ptr(f_out), _ptr(g_out), M, N, K, x.stride(0), w.stride(0), f_out.stride(0) if f_out is not None else 0,
-            g_out.stride(0), _stream())
-    return f_out, g_out
+    return _tn("gm3d_gemm_tn_bf16_gelu", x, w, bias, (f_out, g_out))
 
 
 USE_WS = True             # tall products (M >= 32768) of the mini-PointNet shapes on the weight-stationary kernel (csrc/gemm_ws.hip):
@@ -265,13 +256,7 @@ def ws_ragged_supported(x, w):
 
 def linear_tn_ws(x, w, bias=None, out=None):
     """linear_tn through the weight-stationary streaming kernel (csrc/gemm_ws.hip): bit-identical; for the tall mini-PointNet products."""
-    M, K = x.shape
-    N = w.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-    _launch("gm3d_gemm_tn_bf16_ws", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_ws, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), M, N, K,
-            x.stride(0), w.stride(0), out.stride(0), _stream())
-    return out
+    return _tn("gm3d_gemm_tn_bf16_ws", x, w, bias, (out,))[0]
 
 
 WS_BN = True             # second_conv.0 with the BatchNorm behind it in the product's epilogue (eval: apply + ReLU; train: the statistics)
@@ -312,13 +297,7 @@ def linear_ws_bn_stats(x, w, t, group_rows=32):
 
 def linear_tn_dmaw(x, w, bias=None, out=None, bm=128, bn=256):
     """linear_tn through csrc/gemm_dma.hip with a bm x bn tile (bn = 128 / 192 / 256 columns, N % bn == 0): bit-identical."""
-    M, K = x.shape
-    N = w.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
-    _launch("gm3d_gemm_tn_bf16_dmaw", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_dmaw, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), M,
-            N, K, x.stride(0), w.stride(0), out.stride(0), int(bm), int(bn), _stream())
-    return out
+    return _tn("gm3d_gemm_tn_bf16_dmaw", x, w, bias, (out,), bm, bn)[0]
 
 
 OWN_KT = (2, 4, 6, 8, 16, 18, 24)      # K / 64 values csrc/gemm.hip is unrolled for
@@ -353,33 +332,38 @@ def choose(M, N, K):
     return "dma64x128"
 
 
-def mm(x, w, bias=None, out=None):
-    """x (M,K) @ w (N,K)^T (+ bias) on the kernel `choose` names.  Operands that do not meet the hand-written kernels' layout
-    rules (fp32 parity mode, odd widths) go to torch.mm: never on the bf16 step's path (tools/leftover_sites.py lists none)."""
-    how = choose(x.shape[0], w.shape[0], w.shape[1]) if supported(x, w) else "lib"
-    if how == "lib" and ws_ragged_supported(x, w) and (out is None or (out.stride(1) == 1 and out.stride(0) % 8 == 0)):
-        return linear_tn_ws(x, w, bias, out)       # the 96-wide blocks over 65,536 token rows (Point-M2AE level 0): HBM streams
-    if (how == "lib" and DMA192_RAGGED and USE_DMA and ragged_supported(x, w) and w.shape[0] % 192 == 0 and w.shape[1] % 64 == 0
-            and x.shape[0] >= 8192 and (out is None or (out.stride(1) == 1 and out.stride(0) % 8 == 0))):
-        # N = 192 / 576 (the 192-wide level of the hierarchical model): whole 192-column tiles on the LDS-DMA double-buffer kernel instead of
-        # the ring kernel's 128-column tiles with a ragged second one (a quarter of its MFMA and LDS work wasted)
-        tiles128 = -(-x.shape[0] // 128) * (w.shape[0] // 192)
-        return linear_tn_dmaw(x, w, bias, out, bm=64 if (DMA192_BM64 and tiles128 < 512) else dma_bm(x.shape[0]), bn=192)
-    if how == "lib" and ragged_supported(x, w) and (out is None or (out.stride(1) == 1 and out.stride(0) % 8 == 0)):
+# choose's answers as (kind, arguments of the launch)
+_TARGETS = {"own": ("own", {}), "ring64": ("ring", {"bm": 64}), "ring128": ("ring", {"bm": 128}),
+            **{"dma%dx%d" % (bm, bn): ("dmaw", {"bm": bm, "bn": bn}) for bm in (64, 128) for bn in (128, 192)}}
+_TN = {"own": "gm3d_gemm_tn_bf16", "ring": "gm3d_gemm_tn_bf16_ring", "dmaw": "gm3d_gemm_tn_bf16_dmaw", "ws": "gm3d_gemm_tn_bf16_ws"}
+
+
+def route(x, w, out=None):
+    """What runs x (M,K) @ w (N,K)^T into `out` -> (kind, launch arguments): "own" (csrc/gemm.hip), "ring" with bm, "dmaw" with bm / bn,
+    "ws", "f32" (csrc/gemm_f32.hip, F32_OWN) or "lib" (torch).  Reads shapes, strides, dtypes, addresses and the module switches only:
+    nothing is launched or allocated."""
+    if supported(x, w):                                  # whole 128-column tiles and 64-column K-stages: the shape table
+        return ("ws", {}) if ws_supported(x, w) else _TARGETS[choose(x.shape[0], *w.shape)]
+    if ragged_supported(x, w) and (out is None or (out.stride(1) == 1 and out.stride(0) % 8 == 0)):
+        M, (N, K) = x.shape[0], w.shape
+        if ws_ragged_supported(x, w):                    # the 96-wide blocks over 65,536 token rows (Point-M2AE level 0): HBM streams
+            return "ws", {}
+        if DMA192_RAGGED and USE_DMA and N % 192 == 0 and K % 64 == 0 and M >= 8192:
+            # N = 192 / 576 (the 192-wide level of the hierarchical model): whole 192-column tiles on the LDS-DMA double-buffer kernel
+            # instead of the ring kernel's 128-column tiles with a ragged second one (a quarter of its MFMA and LDS work wasted)
+            tiles128 = -(-M // 128) * (N // 192)
+            return "dmaw", {"bm": 64 if (DMA192_BM64 and tiles128 < 512) else dma_bm(M), "bn": 192}
         # a ragged last column tile alone (K a multiple of the 64-column stage): the ring kernel; a ragged K as well: csrc/gemm.hip
-        if w.shape[1] % 64 == 0:
-            return linear_tn_ring(x, w, bias, out)
-        return linear_tn(x, w, bias, out)
-    if how != "lib" and ws_supported(x, w):
-        return linear_tn_ws(x, w, bias, out)
-    if how == "own":
-        return linear_tn(x, w, bias, out)
-    if how.startswith("ring"):
-        return linear_tn_ring(x, w, bias, out, bm=int(how[4:]))
-    if how.startswith("dma"):
-        bm, bn = how[3:].split("x")
-        return linear_tn_dmaw(x, w, bias, out, bm=int(bm), bn=int(bn))
-    if f32_own(x) and w.dtype == torch.float32 and x.dim() == 2 and w.dim() == 2:
+        return ("ring", {"bm": dma_bm(M)}) if K % 64 == 0 else ("own", {})
+    return ("f32" if _f32_pair(x, w) else "lib"), {}
+
+
+def mm(x, w, bias=None, out=None):
+    """x (M,K) @ w (N,K)^T (+ bias) on what `route` names."""
+    kind, args = route(x, w, out)
+    if kind in _TN:
+        return _tn(_TN[kind], x, w, bias, (out,), *args.values())[0]
+    if kind == "f32":
         return linear_tn_f32(x, w, bias, out)
     y = x @ w.t()
     if bias is not None:
@@ -446,12 +430,11 @@ def mm_nn(x, w, out=None):
     """x (M,N) @ w (N,K) -> (M,K): the input gradient dY . W of a Linear / Conv1d(k=1) layer with weight w (N,K).  bf16 operands
     run as the TN product against a transposed copy of w (one small transposing launch per call: the weights of the layers this
     serves have 32 K .. 512 K elements); anything else goes to torch.mm."""
-    if (ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.dim() == 2 and w.dim() == 2
-            and w.shape[1] % 8 == 0 and w.shape[0] % 8 == 0 and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0):
+    if ENABLED and _rows_ok(x) and w.dtype == torch.bfloat16 and w.dim() == 2 and w.shape[1] % 8 == 0 and w.shape[0] % 8 == 0:
         wt = _transposed_for_mm_nn(w)
         if supported(x, wt) or ragged_supported(x, wt):
             return mm(x, wt, None, out)
-    if f32_own(x) and w.dtype == torch.float32 and x.dim() == 2 and w.dim() == 2:
+    if _f32_pair(x, w):
         return linear_tn_f32(x, transposed(w), None, out)       # the TN kernel on the transposed weight (a copy, no product)
     y = x @ w
     return y if out is None else out.copy_(y)
@@ -462,11 +445,8 @@ POOL_ON_DMA = True        # the pool epilogue on csrc/gemm_dma.hip (128 x 128 / 
 
 def pool16_supported(x, w):
     """conv + max over groups of 16 rows in the weight-stationary kernel's epilogue (the hierarchical model's level-0 groups)"""
-    N, K = w.shape
-    return (USE_WS_POOL and ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and x.dim() == 2
-            and x.shape[0] >= 32768 and x.shape[0] % 16 == 0 and x.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1
-            and x.stride(0) % 8 == 0 and w.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
-            and bool(lib.gm3d_gemm_ws_supported(N, K, 1)))
+    return (USE_WS_POOL and ENABLED and _rows_ok(x) and _rows_ok(w) and x.shape[0] >= 32768 and x.shape[0] % 16 == 0
+            and x.shape[1] == w.shape[1] and bool(lib.gm3d_gemm_ws_supported(w.shape[0], w.shape[1], 1)))
 
 
 def linear_pool(x, w, bias, bias_after_pool, want_rows, group_rows=32):
@@ -502,11 +482,8 @@ OWN_WGRAD = True          # weight-gradient (NT) GEMMs on the hand-written kerne
 def wgrad_supported(dy, x):
     """dy (nb,R,N), x (nb,R,K) bf16 with unit inner stride and a common batch layout; N, K % 8 == 0 (ragged edge tiles), R % 32 == 0."""
     edge = 8 if RAGGED else 128
-    return (ENABLED and OWN_WGRAD and dy.is_cuda and dy.dtype == torch.bfloat16 and x.dtype == torch.bfloat16 and dy.dim() == 3
-            and x.dim() == 3 and dy.shape[:2] == x.shape[:2] and dy.shape[2] % edge == 0 and x.shape[2] % edge == 0
-            and dy.shape[1] % 32 == 0 and dy.stride(2) == 1 and x.stride(2) == 1 and dy.stride(1) % 8 == 0 and x.stride(1) % 8 == 0
-            and dy.stride(1) >= dy.shape[2] and x.stride(1) >= x.shape[2]
-            and dy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and (dy.shape[0] == 1 or (dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0)))
+    return (ENABLED and OWN_WGRAD and _rows_ok(dy, edge, 3) and _rows_ok(x, edge, 3) and dy.shape[:2] == x.shape[:2]
+            and dy.shape[1] % 32 == 0 and (dy.shape[0] == 1 or (dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0)))
 
 
 FUSE_SLAB_SUM = False      # the sum over the row splits inside the NT launch (the last workgroup of a tile adds its slabs in slab order):
@@ -606,7 +583,6 @@ def wgrad_nt_multi(reqs, splits=None, want_splits=False):
     fp32 summation order of a weight gradient follows its splits.  The same product batched differently -- a stack alone, with the
     deferred decoders, inside SegmentedDDPStep's cut, per-request fallback beyond 16 -- may therefore differ in the last bits
     (tests/test_gpu_gemm.py::test_wgrad_multi_default_splits_depend_on_the_batch_only_in_the_last_bits pins the size of that: 1e-6)."""
-    import ctypes
     n = len(reqs)
     VP, I, LL = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_longlong * n
     outs, parts, spl = [], [], []
@@ -647,6 +623,88 @@ def wgrad_nt_multi(reqs, splits=None, want_splits=False):
     return (outs, spl) if want_splits else outs
 
 
+SPLITK = 64              # library fallback of a 2-D weight gradient: row chunks (262,144 rows would otherwise run on a handful of CUs)
+WGRAD_ROW_SPLIT = 4      # library fallback of a batched one: 0 = auto, 1 = off, n = n-way for <= 4-block stacks
+SUM_FEW_ROWS = True      # the chunks' partial products added by gm3d_sum_few_rows (else the two-stage column sum)
+_BMM_OUT_OK = [True]     # torch.bmm(..., out_dtype=, out=) available?
+
+
+def _bmm_f32(dy, x, out=None):
+    """the library's dy[b]^T @ x[b] with an fp32 result, written into `out` where this torch can"""
+    if dy.dtype == torch.float32:
+        return torch.bmm(dy.transpose(1, 2), x) if out is None else torch.bmm(dy.transpose(1, 2), x, out=out)
+    if out is not None and _BMM_OUT_OK[0]:
+        try:
+            return torch.bmm(dy.transpose(1, 2), x, out_dtype=torch.float32, out=out)
+        except (TypeError, RuntimeError):
+            _BMM_OUT_OK[0] = False
+    try:
+        r = torch.bmm(dy.transpose(1, 2), x, out_dtype=torch.float32)
+    except TypeError:
+        r = torch.bmm(dy.transpose(1, 2), x).float()
+    return r if out is None else out.copy_(r)
+
+
+def _wgrad_lib(dy, x, out, flat):
+    """wgrad on the library (shapes the NT kernels do not take).  Long reductions over few output tiles fill a fraction of the 256 CUs:
+    the rows are cut S ways into more batches and the S partial products added in order by our own kernel.  S and the adding kernel
+    are each caller shape's own: SPLITK for one layer's rows (flat), WGRAD_ROW_SPLIT for a stack."""
+    nb, R, N = dy.shape
+    K = x.shape[2]
+    if flat:
+        S = SPLITK if R % SPLITK == 0 and R >= 64 * SPLITK else 1
+    else:
+        S = WGRAD_ROW_SPLIT
+        if S == 0:      # auto: the smallest split that gives the chip >= 512 output tiles of 128x128 while keeping >= 512 rows each
+            S, tiles = 1, nb * max(N // 128, 1) * max(K // 128, 1)
+            while tiles * S < 512 and S < 8 and R % (2 * S) == 0 and R // (2 * S) >= 512:
+                S *= 2
+        elif nb > 4 or R // S < 1024:
+            S = 1
+        if not (R % S == 0 and dy.is_contiguous() and x.is_contiguous()):
+            S = 1
+    if S == 1:
+        return _bmm_f32(dy, x, out)
+    part = _bmm_f32(dy.view(nb * S, R // S, N), x.view(nb * S, R // S, K))
+    if out is None:
+        out = torch.empty(nb, N, K, dtype=torch.float32, device=dy.device)
+    if SUM_FEW_ROWS:
+        _launch("gm3d_sum_few_rows", {"rows": nb * S, "cols": N * K}, lib.gm3d_sum_few_rows, _ptr(part), nb, S, N * K, _ptr(out), _stream())
+    elif flat:
+        _launch("gm3d_colsum_finish", {"rows": S, "cols": N * K}, lib.gm3d_colsum_finish, _ptr(part), S, N * K, N * K, _ptr(out), 0, _stream())
+    else:
+        _launch("gm3d_colsum_finish_batched", {"rows": nb * S, "cols": N * K}, lib.gm3d_colsum_finish_batched, _ptr(part), nb, S * N * K, S,
+                N * K, N * K, _ptr(out), N * K, _stream())
+    return out
+
+
+def wgrad(dy, x, out=None):
+    """dW = dy^T @ x in fp32: dy (R,N), x (R,K) -> (N,K), one layer's weight gradient; or dy (nb,R,N), x (nb,R,K) -> (nb,N,K), every
+    block of a stack at once, into `out` (the parameters' slots of the optimizer's flat gradient buffer) when given.  In this order:
+    the NT kernel (csrc/gemm_nt.hip), the fp32 NT kernel under F32_OWN (csrc/gemm_f32.hip), for one narrow bf16 layer (the 96-wide
+    reconstruction head where the ragged widths are off) dy zero-padded to one 128-column tile, the library."""
+    flat = dy.dim() == 2
+    if flat:
+        plain = dy.is_contiguous() and x.is_contiguous()
+        dy, x = dy.unsqueeze(0), x.unsqueeze(0)
+    nb, R, N = dy.shape
+    K = x.shape[2]
+    if not flat:
+        plain = out is None or (out.stride(2) == 1 and out.stride(1) == K and out.stride(0) == N * K)
+    if plain and wgrad_supported(dy, x):
+        r = wgrad_nt(dy, x, out)
+    elif f32_own(dy) and x.dtype == torch.float32:
+        r = wgrad_nt_f32(dy, x, out)
+    elif flat and plain and 0 < N < 128 and dy.dtype == torch.bfloat16 and wgrad_supported(dy.new_empty(1, R, 128), x):
+        # (the library runs this shape on 32x32 tiles: 88 us per step)
+        pad = torch.zeros(1, R, 128, dtype=dy.dtype, device=dy.device)
+        pad[:, :, :N] = dy
+        r = wgrad_nt(pad, x)[:, :N].contiguous()
+    else:
+        r = _wgrad_lib(dy, x, out, flat)
+    return r[0] if flat else r
+
+
 def tile_rows(M):
     return lib.gm3d_gemm_tile_rows(int(M))
 
@@ -677,7 +735,6 @@ MULTI_TRANSPOSE = True    # the four transposed weight shadows of a stack's back
 def stacked_transposes(groups):
     """[ws_0, ws_1, ...] (each a list of same-shaped (N,K) bf16 weights at a constant stride in one buffer) -> [stacked_transpose(ws_i)]:
     ONE launch for all groups when every group has the regular layout, else one per group."""
-    import ctypes
     ok = MULTI_TRANSPOSE and 1 < len(groups) <= 8
     metas = []
     for ws in groups:

@@ -12,7 +12,7 @@ the whole step safe to replay as a hipGraph on this stack -- see GraphedPretrain
 import torch
 
 from ._capi import lib
-from .embed import _c32, _finish, colsum, splitk_wgrad
+from .embed import _c32, _finish, colsum, linear_bias
 
 
 def _defer_wgrad(dy, x, w=None):
@@ -35,17 +35,10 @@ def _finish64(part, nrows, ncols):
     return out
 
 
-def _ragged_ok(x2, W):
-    """bf16 rows against a weight whose width is a multiple of 8 but not of 128 (the 96-wide reconstruction head): the ring
-    kernel's ragged last column tile."""
-    return (gemm.ENABLED and x2.is_cuda and x2.dtype == torch.bfloat16 and W.dtype == torch.bfloat16 and W.shape[0] % 8 == 0
-            and W.shape[1] % 64 == 0 and W.stride(1) == 1 and W.stride(0) % 8 == 0 and x2.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0)
-
-
 class LinearBiasFn(torch.autograd.Function):
-    """y = x @ W^T + b on rows; x (..,K), W (N,K[,1]) fp32 master, b (N) or None; computed in adt.  bf16: our own MFMA kernels
-    forward and backward (gemm.mm / the ring kernel's ragged tile for widths like 96; input gradient as a TN product against
-    W^T; a width below 128 is zero-padded ONCE for both backward products).  The bias gradient is our own column-sum kernel:
+    """y = x @ W^T + b on rows; x (..,K), W (N,K[,1]) fp32 master, b (N) or None; computed in adt.  Every product through gemm.mm /
+    mm_nn / wgrad, which name the kernel (bf16: our own MFMA kernels, widths like 96 on their ragged tiles; without those a width
+    below 128 is zero-padded ONCE for both backward products).  The bias gradient is our own column-sum kernel:
     PyTorch's multi-block reduction is not hipGraph-replay-safe on this stack."""
 
     @staticmethod
@@ -54,16 +47,7 @@ class LinearBiasFn(torch.autograd.Function):
             shp = x.shape
             x2 = x.reshape(-1, shp[-1]).to(adt).contiguous()
             W = weight_cache.get(w, adt).reshape(w.shape[0], -1)
-            if gemm.supported(x2, W) or gemm.ragged_supported(x2, W):
-                # gemm.mm names the kernel: the tiled families, the ring kernel's ragged last column tile (N = 96), csrc/gemm.hip's
-                # ragged-K form (K = 96), the weight-stationary kernel for the tall ragged shapes
-                y = gemm.mm(x2, W, _c32(b) if b is not None else None)
-            elif _ragged_ok(x2, W):
-                y = gemm.linear_tn_ring(x2, W, _c32(b) if b is not None else None)
-            elif gemm.f32_own(x2):
-                y = gemm.mm(x2, W, _c32(b) if b is not None else None)      # fp32 mode on csrc/gemm_f32.hip (gemm.F32_OWN)
-            else:
-                y = torch.addmm(weight_cache.get(b, adt), x2, W.t()) if b is not None else x2 @ W.t()
+            y = linear_bias(x2, W, b, adt) if b is not None else gemm.mm(x2, W)
             ctx.save_for_backward(x2, w)
             ctx.adt, ctx.shp, ctx.xdt, ctx.has_bias = adt, shp, x.dtype, b is not None
             return y.view(*shp[:-1], w.shape[0])
@@ -86,7 +70,7 @@ class LinearBiasFn(torch.autograd.Function):
                 wt = torch.zeros(K, 128, dtype=adt, device=dy2.device)
                 wt[:, :N] = W.t()
                 dx = gemm.mm(pad, wt).view(ctx.shp).to(ctx.xdt)
-                dW = gemm.wgrad_nt(pad.unsqueeze(0), x2.unsqueeze(0))[0][:N].contiguous().reshape(w.shape)
+                dW = gemm.wgrad(pad, x2)[:N].contiguous().reshape(w.shape)
                 return dx, dW, db, None
             dx = gemm.mm_nn(dy2, W).view(ctx.shp).to(ctx.xdt)
             dW = _defer_wgrad(dy2, x2, w).reshape(w.shape)

@@ -28,7 +28,7 @@ _BLOCK_RE = re.compile(r"^(.*\.blocks)\.(\d+)\.(.+)$")
 def _kind_key(name):
     """Sort key that puts the same-kind weights of one block stack next to each other, in block order
     (X.blocks.0.mlp.fc1.weight, X.blocks.1.mlp.fc1.weight, ...): the stack's batched weight-gradient GEMM then has ONE
-    contiguous (nblk, N, K) destination in the flat gradient buffer and writes it directly (fused._wgrad_batched)."""
+    contiguous (nblk, N, K) destination in the flat gradient buffer and writes it directly (gemm.wgrad)."""
     m = _BLOCK_RE.match(name)
     return (0, "", "", 0) if m is None else (1, m.group(1), m.group(3), int(m.group(2)))
 

@@ -133,7 +133,7 @@ class SegmentedStep:
         views, have, zero = self.seg_views[seg], [], []
         for v, g in zip(views, grads):
             if g is not None and g.data_ptr() == v.data_ptr():
-                continue                      # written into its slot by the backward node itself (fused._wgrad_batched)
+                continue                      # written into its slot by the backward node itself (gemm.wgrad)
             (have if g is not None else zero).append((v, g))
         if have:
             torch._foreach_copy_([v for v, _ in have], [g for _, g in have])

@@ -119,3 +119,58 @@ def test_group_max_predicate_and_op(C, K):
     x = torch.randn(5, K, C, device="cuda").requires_grad_(True)
     assert heads.group_max_supported(x)
     assert torch.equal(heads.GroupMaxFn.apply(x), x.detach().amax(1))
+
+
+# ------------------------------------------------------------------ GPU: the dispatcher's tails and the one weight-gradient entry
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,N,K", [(33, 96, 72), (64, 128, 64)])
+def test_fp32_products_are_the_library_s_own_without_f32_own(M, N, K):
+    from gm3d_amd import gemm
+    assert gemm.F32_OWN is False
+    g = torch.Generator(device="cuda").manual_seed(M + N + K)
+    x, dy = torch.randn(M, K, device="cuda", generator=g), torch.randn(M, N, device="cuda", generator=g)
+    w = torch.randn(N, K, device="cuda", generator=g)
+    assert gemm.route(x, w) == ("lib", {})
+    assert torch.equal(gemm.mm(x, w), x @ w.t())
+    assert torch.equal(gemm.mm_nn(dy, w), dy @ w)
+
+
+@pytest.mark.gpu
+def test_linear_bias_fn_fp32_forward_is_addmm():
+    from gm3d_amd import heads
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.randn(40, 384, device="cuda", generator=g)
+    w, b = torch.randn(96, 384, device="cuda", generator=g) / 20, torch.randn(96, device="cuda", generator=g)
+    assert torch.equal(heads.LinearBiasFn.apply(x, w, b, torch.float32), torch.addmm(b, x, w.t()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(64, 96, 72), (2, 64, 128, 128)])
+def test_wgrad_is_the_fp32_nt_kernel_under_f32_own(shape, monkeypatch):
+    from gm3d_amd import gemm
+    monkeypatch.setattr(gemm, "F32_OWN", True)
+    g = torch.Generator(device="cuda").manual_seed(sum(shape))
+    dy = torch.randn(*shape[:-2], shape[-2], device="cuda", generator=g)
+    x = torch.randn(*shape[:-2], shape[-1], device="cuda", generator=g)
+    if dy.dim() == 2:
+        assert torch.equal(gemm.wgrad(dy, x), gemm.wgrad_nt_f32(dy.unsqueeze(0), x.unsqueeze(0))[0])
+    else:
+        assert torch.equal(gemm.wgrad(dy, x), gemm.wgrad_nt_f32(dy, x))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nb,R,N,K", [(1, 64, 128, 128), (4, 96, 136, 72), (1, 48, 128, 128)])
+def test_wgrad_is_the_nt_kernel_for_bf16_and_the_library_off_its_rows(nb, R, N, K):
+    from gm3d_amd import gemm
+    g = torch.Generator(device="cuda").manual_seed(nb + R + N + K)
+    dy = torch.randn(nb, R, N, device="cuda", generator=g).bfloat16()
+    x = torch.randn(nb, R, K, device="cuda", generator=g).bfloat16()
+    if R % 32 == 0:
+        assert torch.equal(gemm.wgrad(dy, x), gemm.wgrad_nt(dy, x))
+        assert torch.equal(gemm.wgrad(dy[0], x[0]), gemm.wgrad_nt(dy[:1], x[:1])[0])
+        return
+    assert not gemm.wgrad_supported(dy, x)            # R = 48: no multiple of the NT kernel's 32-row stage -> torch.bmm
+    want = torch.bmm(dy.float().transpose(1, 2), x.float())
+    for got in (gemm.wgrad(dy, x), gemm.wgrad(dy[0], x[0]).unsqueeze(0)):
+        assert got.dtype == torch.float32
+        assert float((got - want).abs().max()) <= 2.0 ** -8 * float(want.abs().max())

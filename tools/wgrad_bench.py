@@ -3,7 +3,7 @@ at the step's shapes.  python tools/wgrad_bench.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from gm3d_amd import gemm, fused
+from gm3d_amd import gemm
 
 dev = torch.device("cuda")
 
@@ -57,7 +57,7 @@ if __name__ == "__main__":
       own = timeit(lambda: gemm.wgrad_nt(dy, x, out))
       was = gemm.OWN_WGRAD
       gemm.OWN_WGRAD = False
-      lib_t = timeit(lambda: fused._wgrad_batched(dy, x, out))
+      lib_t = timeit(lambda: gemm.wgrad(dy, x, out))
       gemm.OWN_WGRAD = was
       fl = 2.0 * nb * R * N * K
       print("%-28s %10.1f %10.1f %8.2f   %d   (own %.0f TFLOP/s)" % (str((nb, R, N, K)), own, lib_t, lib_t / own,
