@@ -38,6 +38,7 @@ SOURCES = {
     "svm.hip": ["-ffp-contract=off"],
     "mask.hip": ["-ffp-contract=off"],
     "knn_probe.hip": ["-ffp-contract=off"],
+    "dataset.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

@@ -53,6 +53,13 @@ __device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx,
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
+// float -> uint32 whose unsigned order is the float order (-0 == +0, NaN above +inf like a sort puts it last)
+__device__ __forceinline__ unsigned int ordered_key(float v) {
+    if (v == 0.f) v = 0.f;                                   // -0 -> +0: equal values tie on the index
+    const unsigned int u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 // ---- DPP cross-lane moves (gfx9 encodings) -------------------------------------------
 // quad_perm [1,0,3,2] = 0xB1, [2,3,0,1] = 0x4E, row_half_mirror 0x141, row_mirror 0x140,
 // row_bcast15 0x142, row_bcast31 0x143, wave_shr1 0x138.

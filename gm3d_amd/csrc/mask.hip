@@ -16,13 +16,6 @@ namespace gm3d {
 
 constexpr int MC_MAX = 512;
 
-// float -> uint32 whose unsigned order is the float order (-0 == +0, NaN above +inf like a sort puts it last)
-__device__ __forceinline__ unsigned int ordered_key(float v) {
-    if (v == 0.f) v = 0.f;                                   // -0 -> +0: equal values tie on the index
-    const unsigned int u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(MC_MAX) void mask_centers_kernel(const float* __restrict__ in, const int* __restrict__ start, int mode,
                                                               int G, int num_mask, unsigned char* __restrict__ mask_bool,
                                                               long long* __restrict__ order, int id_pitch) {

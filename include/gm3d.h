@@ -793,6 +793,28 @@ int gm3d_knn_probe_classify(const float *Xn, const float *Qn, int n, int m, int 
                             float T, const long long *test_labels, long long *top5, float *probs, long long *correct,
                             gm3d_stream_t stream);
 
+/* ---- Batch assembly from a device-resident dataset (gm3d_amd/csrc/dataset.hip) -------------------------------------------------------
+ * gm3d_sample_normalize: what the reference's datasets do per sample on the host, for a whole batch in one launch:
+ *   Point-MAE_SA3D/datasets/ShapeNet55Dataset.py:45-67 (random_sample: shuffle + [:num]; pc_norm), ModelNetDataset.py:138-145 and
+ *   ScanObjectNNDataset.py:33-44 (the train split's shuffle of all points), with the collate and the host-to-device copy behind them.
+ * data (M,N0,3) f32 the resident dataset; cloud_idx (B) int64 the batch's clouds, any order, repeats allowed (an index outside
+ * 0..M-1 is clamped into it); keys (B,N0) f32 one draw per point, made by the caller (the kernel draws nothing); out (B,num,3) f32;
+ * idx_out (B,num) int32 the selected point indices, or NULL.
+ * Order: row j of cloud b is the point i with the j-th smallest (ordered_key(keys[b,i]), i), ordered_key the order-preserving integer
+ * of gm3d_mask_centers (-0 == +0, NaN above +inf).  The order is strict and total: idx_out[b] always holds num distinct indices in
+ * 0..N0-1, all keys equal give data[cloud_idx[b], :num], and every output is a pure function of the inputs (an in-LDS bitonic sort of
+ * packed 64-bit pairs, N0 padded to a power of two with maximal pairs; no atomics).  Independent uniform keys give a uniformly random
+ * ordered subset, with num == N0 a uniformly random permutation.
+ * normalize = 0: rows are bit copies of the source points.  normalize = 1: pc_norm of the selected points in fp32 -- minus their mean
+ * (a workgroup tree sum / num), divided (IEEE) by the square root of the largest squared norm (x*x + y*y) + z*z, no FMA; selected
+ * points that all coincide give 0 / 0 like the reference.
+ * One workgroup of min(1024, max(64, P/2)) threads per cloud, P = N0 rounded up to a power of two; LDS 8 P bytes dynamic (64 KiB at
+ * N0 = 8192) + 64 bytes static.
+ * Limits, checked on the host before any launch: GM3D_EINVAL for a NULL data / cloud_idx / keys / out, B < 1, M < 1, N0 < 1, num < 1,
+ * num > N0, normalize not 0 or 1; GM3D_EUNSUPPORTED for N0 > 8192. */
+int gm3d_sample_normalize(const float *data, const long long *cloud_idx, const float *keys, int B, int M, int N0, int num,
+                          int normalize, float *out, int *idx_out, gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
