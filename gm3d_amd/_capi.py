@@ -156,6 +156,7 @@ SIGNATURES = {
     "gm3d_gemm_nt_f32_splits": [_i, _i, _i, _i],
     "gm3d_gemm_nt_f32_slab_rows": [_i, _i],
     "gm3d_sample_normalize": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "gm3d_augment": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 

@@ -815,6 +815,54 @@ int gm3d_knn_probe_classify(const float *Xn, const float *Qn, int n, int m, int 
 int gm3d_sample_normalize(const float *data, const long long *cloud_idx, const float *keys, int B, int M, int N0, int num,
                           int normalize, float *out, int *idx_out, gm3d_stream_t stream);
 
+/* ---- Point-cloud augmentations as one launch (gm3d_amd/csrc/augment.hip) -------------------------------------------------------------
+ * gm3d_augment: an ordered program of 1..GM3D_AUG_MAX_OPS transforms of Point-MAE_SA3D/datasets/data_transforms.py applied IN PLACE to
+ * pc (B,N,3) f32 (the one entry point that writes its input: the reference's transforms do).  One workgroup per cloud, one launch.
+ * The program is read from host memory at call time (ops (nops) int, params (nops,3) f32) and handed to the kernel by value: no
+ * device allocation, no copy, no synchronisation; a captured graph bakes the program in and replays it on whatever the draw tensors
+ * hold.  The kernel draws nothing.
+ *
+ *   op (ops[j] & 0xff)         draws/cloud  params[j]        what it does to every point (x, y, z) of cloud b
+ *   GM3D_AUG_ROTATE          :6-18     1    -                angle = 2 pi u; c, s = cos, sin in double, rounded to f32;
+ *                                                            x' = x c - z s, y' = y, z' = x s + z c
+ *   GM3D_AUG_SCALE           :51-63    3    lo, span         p * (u * span + lo)
+ *   GM3D_AUG_TRANSLATE       :65-76    3    t                p + (u * 2 - 1) * t
+ *   GM3D_AUG_SCALE_TRANSLATE :20-35    3+3  lo, span, t      p * (u * span + lo) + (u' * 2 - 1) * t: bit-identical to gm3d_scale_translate
+ *   GM3D_AUG_JITTER          :37-49    0    std, clip        p + clamp(point_z[b,i] * std, -clip, clip)
+ *   GM3D_AUG_DROPOUT         :79-94    1    max_ratio        point i becomes point 0 (as it stands when the op starts) iff
+ *                                                            (double)point_u[b,i] <= (double)u * (double)max_ratio
+ *   GM3D_AUG_FLIP            :96-118   3    upright axis     draws [gate, lower axis, higher axis] (the two axes that are not upright, in
+ *                            (0, 1 or 2)                     ascending order): if (double)gate < 0.95, each of them whose (double)draw < 0.5
+ *                                                            becomes max over the cloud's points - coordinate
+ * Every product and sum is rounded separately in f32 (no FMA), the flip's maximum is exact (NaN coordinates are skipped by it).
+ * ops[j] | GM3D_AUG_FINAL (parity tests): the op's draws hold the final quantity instead of the uniform -- SCALE: the scales;
+ * TRANSLATE: the shifts; SCALE_TRANSLATE: scales, then shifts; DROPOUT: the ratio point_u is compared with; JITTER: point_z is the noise
+ * before the clamp (std is not applied).  ROTATE and FLIP take their uniforms either way.  Same kernel code: the flag skips one map.
+ *
+ * cloud_u holds B * D f32, D the sum of the draws/cloud over the program (what one torch.rand(B, D) makes), as one block per draw
+ * group in program order: a group of cnt = 1 or 3 draws that starts at column c (the sum of the counts in front of it) is the
+ * (B,cnt) row-major block at cloud_u + B * c; SCALE_TRANSLATE is two groups, scales then shifts -- alone it is gm3d_scale_translate's
+ * (2,B,3).  point_u (B,N) f32 uniforms: needed by DROPOUT; point_z (B,N,3) f32 normals: needed by JITTER; either may be NULL
+ * otherwise, and cloud_u when D = 0.
+ * Limits, checked on the host before any launch: GM3D_EINVAL for a NULL pc / ops / params, N < 1, B < 0, nops outside
+ * 1..GM3D_AUG_MAX_OPS, an unknown op code or flag bit, an upright axis other than 0, 1, 2, more than one DROPOUT or more than one
+ * JITTER in a program (there is one point_u and one point_z), or a missing draw tensor the program needs.  B = 0 returns GM3D_OK
+ * without a launch.  No limit on N: min(1024, N rounded up to 64) threads per cloud, 408 bytes of LDS. */
+enum {
+    GM3D_AUG_NONE = 0,
+    GM3D_AUG_ROTATE = 1,
+    GM3D_AUG_SCALE = 2,
+    GM3D_AUG_TRANSLATE = 3,
+    GM3D_AUG_SCALE_TRANSLATE = 4,
+    GM3D_AUG_JITTER = 5,
+    GM3D_AUG_DROPOUT = 6,
+    GM3D_AUG_FLIP = 7,
+    GM3D_AUG_FINAL = 0x100,
+    GM3D_AUG_MAX_OPS = 8
+};
+int gm3d_augment(float *pc, int B, int N, int nops, const int *ops, const float *params, const float *cloud_u,
+                 const float *point_u, const float *point_z, gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
