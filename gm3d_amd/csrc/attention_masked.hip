@@ -316,6 +316,10 @@ template <int HD>
 __global__ __launch_bounds__(128) void mattn_fwd_f32_kernel(const float* __restrict__ qkv, const unsigned* __restrict__ mask,
                                                             float* __restrict__ out, float* __restrict__ lse, int B, int T, int H, int W,
                                                             float scale) {
+    // `s * scale - m` must not become one fma: the pass that takes the maximum rounds the product, and where scale is no power of
+    // two (HD = 32) the fused form gives the largest logit exp(+-1e-7) instead of exp(0) = 1 -- a row with ONE allowed key then
+    // returns its v off by an ulp.  (__fmul_rn is a plain product to the compiler and is contracted all the same.)
+#pragma clang fp contract(off)
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)B * H * T) return;
     const int q = (int)(gid % T), h = (int)((gid / T) % H), b = (int)(gid / ((long long)T * H));
@@ -342,7 +346,7 @@ __global__ __launch_bounds__(128) void mattn_fwd_f32_kernel(const float* __restr
             float s = 0.f;
 #pragma unroll
             for (int d = 0; d < HD; ++d) s = fmaf(qv[d], base[(size_t)j * rs + os + d], s);
-            const float p = expf(s * scale - m);
+            const float p = expf(s * scale - m);           // contract(off): the largest logit gives exp(0) = 1 exactly
             l += p;
 #pragma unroll
             for (int d = 0; d < HD; ++d) o[d] = fmaf(p, base[(size_t)j * rs + 2 * os + d], o[d]);
@@ -359,6 +363,7 @@ __global__ __launch_bounds__(128) void mattn_bwd_f32_kernel(const float* __restr
                                                             const float* __restrict__ out, const float* __restrict__ dout,
                                                             const float* __restrict__ lse, float* __restrict__ dqkv, int B, int T, int H,
                                                             int W, float scale) {
+#pragma clang fp contract(off)                       // the forward's logit s * scale, bit for bit (see mattn_fwd_f32_kernel)
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)B * H * T) return;
     const int i = (int)(gid % T), h = (int)((gid / T) % H), b = (int)(gid / ((long long)T * H));

@@ -32,6 +32,32 @@ def test_radius_mask_bits_kernel():
         assert torch.equal(ops.radius_mask_bits(c.cuda(), None, radius), ops.pack_mask(HR.far_mask(c, radius).cuda()))
 
 
+@pytest.mark.parametrize("G", [77, 512])
+@pytest.mark.parametrize("with_vis", [False, True])
+def test_radius_mask_bits_at_the_boundary(G, with_vis):
+    """Generic centres never put a pair AT the radius.  Lattice centres k / 8, k in -6..6, with radius 0.5 do: every coordinate
+    difference, its square and the sum are exact in fp32, d^2 == r^2 == 0.25 occurs (e.g. a difference of (4, 0, 0) / 8), and
+    `>=` means such a pair is blocked.  Bit-exact against the packed boolean expression, d^2 formed as sqdist3 forms it."""
+    from gm3d_amd import ops
+    g = torch.Generator().manual_seed(G)
+    B, radius = 3, 0.5
+    c = torch.randint(-6, 7, (B, G, 3), generator=g).float() / 8
+    vis = torch.rand(B, G, generator=g) < 0.6 if with_vis else None
+    d = c[:, :, None, :] - c[:, None, :, :]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    assert d2.dtype == torch.float32
+    r2 = torch.tensor(radius, dtype=torch.float32) * torch.tensor(radius, dtype=torch.float32)
+    seen = torch.ones(B, G, G, dtype=torch.bool) if vis is None else vis[:, :, None] & vis[:, None, :]
+    ties = (d2 == r2) & seen
+    assert int(ties.sum()) > 0 and bool((d2 < r2).any()) and bool((d2 > r2).any())
+    want = ~seen | (d2 >= r2)
+    got = ops.radius_mask_bits(c.cuda(), None if vis is None else vis.cuda(), radius)
+    assert torch.equal(got, ops.pack_mask(want.cuda()))
+    # the ties themselves: blocked
+    unpacked = ((got.cpu().long()[:, :, :, None] >> torch.arange(32)) & 1).bool().reshape(B, G, -1)[:, :, :G]
+    assert bool(unpacked[ties].all())
+
+
 # Max-pool winners (including EXACT ties, which do occur: torch.amax shares the gradient between tied maxima, a plain argmax does
 # not), ReLU / LeakyReLU sign patterns (a BatchNorm bias gradient in the loss head is a sum over only B*64 rows: ONE
 # pre-activation within 1e-5 of zero moves it by 1 %), Chamfer nearest neighbours, the guided mask and the sign pattern of the
