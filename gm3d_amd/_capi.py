@@ -157,6 +157,9 @@ SIGNATURES = {
     "gm3d_gemm_nt_f32_slab_rows": [_i, _i],
     "gm3d_sample_normalize": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "gm3d_augment": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "gm3d_linprobe_slices": [_i],
+    "gm3d_linprobe_train": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _f] + [_vp] * 9 + [_vp],
+    "gm3d_linprobe_eval": [_vp, _vp, _i, _i, _i] + [_vp] * 7 + [_vp],
 }
 
 

@@ -40,6 +40,7 @@ SOURCES = {
     "knn_probe.hip": ["-ffp-contract=off"],
     "dataset.hip": ["-ffp-contract=off"],
     "augment.hip": ["-ffp-contract=off"],
+    "linprobe.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

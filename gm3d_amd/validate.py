@@ -132,18 +132,42 @@ def evaluate_knn(train_features, train_labels, test_features, test_labels, ks=(1
     return out
 
 
+def evaluate_linear(train_features, train_labels, test_features, test_labels, num_classes=None, **probe_kwargs):
+    """The reference's third probe (Point-MAE_SA3D/main_linprob.py:219-263): BatchNorm1d(affine=False) + Linear trained with SGD on
+    the frozen features, on the GPU (gm3d_amd.linear_probe).  Accepts token features (n,T,C) or already pooled (n,C), pooled as
+    evaluate_svm pools; labels are class indices.  num_classes None: max label + 1 (one more host read).  probe_kwargs:
+    LinearProbe's (batch_size, epochs, ...) and fit's weight / orders; a batch_size above the training rows is lowered to them.
+    -> {"acc1", "acc5", "max_acc1", "history"}, in percent."""
+    from . import linear_probe
+
+    def dev(t, dtype):
+        t = torch.as_tensor(t)
+        return (t if t.is_cuda else t.to("cuda")).to(dtype)
+
+    def pooled(f):
+        f = dev(f, torch.float32)
+        return (pool_features(f) if f.dim() == 3 else f).contiguous()
+    xtr, xte = pooled(train_features), pooled(test_features)
+    ytr, yte = dev(train_labels, torch.int64).view(-1).contiguous(), dev(test_labels, torch.int64).view(-1).contiguous()
+    if num_classes is None:
+        num_classes = max(int(torch.maximum(ytr.max(), yte.max()).item()) + 1, 2)
+    probe_kwargs["batch_size"] = min(probe_kwargs.get("batch_size", 512), xtr.shape[0])
+    return linear_probe.linear_probe(xtr, ytr, xte, yte, num_classes, **probe_kwargs)
+
+
 @torch.no_grad()
 def validate(model, extra_train_dataloader, test_dataloader, npoints=None, device="cuda", bf16=False, svm_backend="sklearn",
-             probe="svm", knn_ks=(10, 20, 100, 200), knn_T=0.07):
+             probe="svm", knn_ks=(10, 20, 100, 200), knn_T=0.07, linear_kwargs=None):
     """Loaders yield (taxonomy_ids, model_ids, (points, label)) like the reference's ModelNet loaders (:428-431).
     Returns the SVM accuracy (computed on every rank from the gathered features, like the reference).  npoints None:
     default_npoints(model).  svm_backend "hip" keeps the gathered features on the GPU and solves there.
     probe "svm" (default): the SVM accuracy; "knn": evaluate_knn's {k: (top-1 %, top-5 %)} on the same gathered features, no SVM;
-    "both": (SVM accuracy, that dict)."""
+    "both": (SVM accuracy, that dict); "linear": evaluate_linear's dict (linear_kwargs: its keyword arguments), no SVM;
+    "all": (SVM accuracy, the k-NN dict, the linear dict)."""
     if svm_backend not in ("sklearn", "hip"):
         raise ValueError("unknown SVM backend %r (sklearn or hip)" % (svm_backend,))
-    if probe not in ("svm", "knn", "both"):
-        raise ValueError("unknown probe %r (svm, knn or both)" % (probe,))
+    if probe not in ("svm", "knn", "both", "linear", "all"):
+        raise ValueError("unknown probe %r (svm, knn, both, linear or all)" % (probe,))
     was_training = model.training
     model.eval()
     feats = {}
@@ -155,7 +179,11 @@ def validate(model, extra_train_dataloader, test_dataloader, npoints=None, devic
             l.append(label.view(-1))
         feats[split] = (gather_tensor(torch.cat(f, 0)), gather_tensor(torch.cat(l, 0)))
     model.train(was_training)
-    knn = None
+    knn = linear = None
+    if probe in ("linear", "all"):
+        linear = evaluate_linear(feats["train"][0], feats["train"][1], feats["test"][0], feats["test"][1], **(linear_kwargs or {}))
+        if probe == "linear":
+            return linear
     if probe != "svm":
         knn = evaluate_knn(feats["train"][0], feats["train"][1], feats["test"][0], feats["test"][1], ks=knn_ks, T=knn_T)
         if probe == "knn":
@@ -165,4 +193,6 @@ def validate(model, extra_train_dataloader, test_dataloader, npoints=None, devic
     else:
         acc = evaluate_svm(feats["train"][0].cpu().numpy(), feats["train"][1].cpu().numpy(),
                            feats["test"][0].cpu().numpy(), feats["test"][1].cpu().numpy())
+    if probe == "all":
+        return acc, knn, linear
     return acc if probe == "svm" else (acc, knn)

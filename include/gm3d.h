@@ -863,6 +863,47 @@ enum {
 int gm3d_augment(float *pc, int B, int N, int nops, const int *ops, const float *params, const float *cloud_u,
                  const float *point_u, const float *point_z, gm3d_stream_t stream);
 
+/* ---- Linear probe of pretrained features (gm3d_amd/csrc/linprobe.hip) ----------------------------------------------------------------
+ * The linear probe of Point-MAE_SA3D/main_linprob.py:219-263 on cached features: BatchNorm1d(affine=False, eps=1e-6) -> Linear,
+ * cross-entropy, SGD(momentum, weight decay 0), all in fp32 (the reference's fp16 autocast is not reproduced).
+ * X (n,d) f32 training features, y (n) int64 class indices (a label outside 0..ncls-1 is clamped into it: the caller checks the
+ * range), order (T*batch) int32 the training rows of iteration t at order[t*batch .. (t+1)*batch) (clamped into 0..n-1), lr (T) f32
+ * the rate of every iteration, W (ncls,d), mom_w (ncls,d), mom_b (ncls), running_mean (d), running_var (d), losses (T), and bias2
+ * (2,ncls): slot t & 1 holds the bias BEFORE iteration t, so after T iterations the bias is bias2[T & 1].
+ * One training iteration on the batch rows B (|B| = batch), per column j and class c:
+ *   mean_j = sum_i x_ij / batch, var_j = sum_i (x_ij - mean_j)^2 / batch (two passes), x^_ij = (x_ij - mean_j) / sqrt(var_j + 1e-6),
+ *   running_mean_j = 0.9 running_mean_j + 0.1 mean_j, running_var_j = 0.9 running_var_j + 0.1 var_j batch / (batch - 1),
+ *   z = x^ W^T + b, losses[t] = mean_i (log sum_c exp(z_ic - max_i) + max_i - z_i[y_i]),
+ *   dz = (softmax(z) - onehot(y)) / batch, dW = dz^T x^, db = sum_i dz_i (nothing flows into the BatchNorm),
+ *   mu = momentum mu + g, p = p - lr[t] mu for W and b alike (torch.optim.SGD; mu starts at 0, so mu = g on the first step).
+ * gm3d_linprobe_train runs the iterations t_begin .. t_end - 1 in t_end - t_begin + 1 launches of ceil(d / 16) workgroups, one per
+ *   16 columns: launch K(t) finishes iteration t-1 (sums the partial logits of all column slices in slice order plus the bias,
+ *   softmax, dz, dW / momentum / weights of its slice; workgroup 0: db, bias, loss) and starts iteration t (gather, statistics,
+ *   running statistics, partial logits of its slice with the weights just updated); the first launch only starts, the last only
+ *   finishes.  A workgroup never waits for another inside a launch; no cooperative launch, no float atomics; stream-ordered, no host
+ *   synchronisation.  Every reduction runs in an order fixed by the shapes (linprobe.hip lists them): equal inputs give equal bits.
+ *   Scratch: xhat (batch,d) f32 16-byte aligned, part (2 * gm3d_linprobe_slices(d) * ncls * batch) f32; both are written before they
+ *   are read and must stay untouched between two calls that continue one fit.  t_end == t_begin launches nothing.
+ *   LDS: 94,720 bytes dynamic, none static; __launch_bounds__(512); one workgroup per CU.
+ * gm3d_linprobe_eval: z = ((Q - running_mean) / sqrt(running_var + 1e-6)) W^T + bias for all m rows of Q (m,d) f32, one fmaf per
+ *   column onto the running sum, columns ascending, then + bias; the classes are ranked by (logit descending, class ascending, -0 ==
+ *   +0, NaN above +inf).  logits (m,ncls) f32 or NULL; pred (m) int64 = the first class, or NULL; yq (m) int64 or NULL: correct[0] +=
+ *   the rows whose first class is the label, correct[1] += the rows with the label among the first min(5, ncls) classes (int64
+ *   atomics; with yq NULL correct is not touched and may be NULL).  One launch of ceil(m / 64) workgroups of 256 threads.
+ * gm3d_linprobe_slices: ceil(d / 16), the number of column slices (0 for d < 1).
+ * Limits (GM3D_EINVAL for n < 1, m < 0, d < 1, ncls < 1, batch < 2, batch > n, t_begin < 0, t_end < t_begin, momentum outside [0, 1)
+ * or NaN, a NULL required pointer, a misaligned X or xhat; GM3D_EUNSUPPORTED beyond the kernels' range; all checked on the host
+ * before any launch):
+ *   1 <= n <= 16384, m >= 0, 8 <= d <= 1024, d % 8 == 0, 2 <= ncls <= 64, 2 <= batch <= min(n, 1024).
+ * m == 0 returns GM3D_OK after the shape checks, launching nothing. */
+int gm3d_linprobe_slices(int d);
+int gm3d_linprobe_train(const float *X, const long long *y, int n, int d, int ncls, int batch, const int *order, const float *lr,
+                        int t_begin, int t_end, float momentum, float *W, float *mom_w, float *bias2, float *mom_b,
+                        float *running_mean, float *running_var, float *xhat, float *part, float *losses, gm3d_stream_t stream);
+int gm3d_linprobe_eval(const float *Q, const long long *yq, int m, int d, int ncls, const float *W, const float *bias,
+                       const float *running_mean, const float *running_var, float *logits, long long *pred, long long *correct,
+                       gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
