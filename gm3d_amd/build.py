@@ -41,6 +41,7 @@ SOURCES = {
     "dataset.hip": ["-ffp-contract=off"],
     "augment.hip": ["-ffp-contract=off"],
     "linprobe.hip": ["-ffp-contract=off"],
+    "reconstruct.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

@@ -588,3 +588,51 @@ def attention_masked(qkv, bits, num_heads, scale):
     """qkv (B,T,3*H*hd), hd in {16,32,64}, T <= 512; bits = pack_mask(mask) of a SYMMETRIC (B,T,T) bool mask (True = not allowed)
     or None -> (B,T,H*hd).  A query with no allowed key yields zeros.  (The hierarchical Point-M2AE encoder's attention.)"""
     return _AttentionMasked.apply(qkv, bits, num_heads, scale)
+
+
+# ------------------------------------------------------------------ reconstructed clouds (models/Point_MAE.py:428-439)
+@torch.no_grad()
+def reconstruct_assemble(pred, neighborhood, center, vis_ids, mask_ids, flat=False):
+    """The `vis` branch of the reference's Point_MAE.forward in one launch (gm3d_reconstruct_assemble): pred (B,M,3k) f32/bf16 -- a
+    batch-strided view such as pix_pred[:, -M:] is taken as it is --, neighborhood (B,G,k,3) f32 centre-relative, center (B,G,3) f32,
+    vis_ids (B,V) / mask_ids (B,M) int64 (row-strided views are taken as they are), V + M = G
+    -> (dense (B*G*k,3) f32, full_center (B*G,3) f32), detached (there is no backward).
+    flat=False: per cloud, [visible patches in vis_ids order | rebuilt patches in mask_ids order], full_center in the same order.
+    flat=True: the reference's layout -- all clouds' visible patches, then all rebuilt ones; full_center all MASKED centres, then all
+    visible ones."""
+    neighborhood, center = neighborhood.detach(), center.detach()
+    _require(neighborhood, torch.float32, "neighborhood")
+    _require(center, torch.float32, "center")
+    _require(vis_ids, torch.int64, "vis_ids", contiguous=False)
+    _require(mask_ids, torch.int64, "mask_ids", contiguous=False)
+    if neighborhood.dim() != 4 or neighborhood.size(3) != 3 or tuple(center.shape) != tuple(neighborhood.shape[:2]) + (3,):
+        raise RuntimeError("neighborhood must be (B,G,k,3) and center (B,G,3)")
+    B, G, k, _ = neighborhood.shape
+    if vis_ids.dim() != 2 or mask_ids.dim() != 2 or vis_ids.size(0) != B or mask_ids.size(0) != B:
+        raise RuntimeError("vis_ids must be (B,V) and mask_ids (B,M)")
+    V, M = vis_ids.size(1), mask_ids.size(1)
+    if V + M != G:
+        raise RuntimeError("V + M = %d + %d must equal G = %d" % (V, M, G))
+    if (V > 1 and vis_ids.stride(1) != 1) or (M > 1 and mask_ids.stride(1) != 1):
+        raise RuntimeError("the id rows must be dense (stride 1 along dim 1)")
+    dt = _capi.GM3D_F32
+    if M > 0:
+        pred = pred.detach()
+        _require(pred, None, "pred", contiguous=False)
+        if pred.dtype not in _DT:
+            raise RuntimeError("pred must be float32 or bfloat16")
+        if tuple(pred.shape) != (B, M, 3 * k) or pred.stride(2) != 1 or pred.stride(1) != 3 * k:
+            raise RuntimeError("pred must be (B,M,3k) = (%d,%d,%d) with dense rows" % (B, M, 3 * k))
+        dt = _DT[pred.dtype]
+    dense = torch.empty(B * G * k, 3, dtype=torch.float32, device=neighborhood.device)
+    full_center = torch.empty(B * G, 3, dtype=torch.float32, device=neighborhood.device)
+    if B == 0:
+        return dense, full_center
+
+    def bstride(t, need):          # a batch of one may carry any stride along dim 0
+        return t.stride(0) if B > 1 else max(t.stride(0), need)
+    _launch("gm3d_reconstruct_assemble", {"B": B, "G": G, "k": k, "M": M, "flat": bool(flat)}, lib.gm3d_reconstruct_assemble,
+            _ptr(pred) if M > 0 else None, bstride(pred, M * 3 * k) if M > 0 else 0, _ptr(neighborhood), _ptr(center),
+            _ptr(vis_ids) if V > 0 else None, bstride(vis_ids, V) if V > 0 else 0, _ptr(mask_ids) if M > 0 else None,
+            bstride(mask_ids, M) if M > 0 else 0, B, G, k, V, M, 1 if flat else 0, _ptr(dense), _ptr(full_center), dt, _stream())
+    return dense, full_center

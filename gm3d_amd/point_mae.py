@@ -129,21 +129,18 @@ class Point_MAE(nn.Module):
             return heads.LinearBiasFn.apply(x_rec, c.weight, c.bias, heads._adt())
         return nn.functional.linear(x_rec, c.weight.squeeze(-1), c.bias)
 
-    def forward(self, pts, noaug=False, vis=False, mask_noise=None, mask_start=None, mask=None, **kwargs):
-        """P/:391-441 (Point-MAE pre-training loss; `vis` is a plotting aid and is not provided).  mask / mask_noise / mask_start:
-        see MaskTransformer.select.  With any of them (or MAE_encoder.device_mask) on a GPU the step is the replayable one:
-        token and position gathers through heads.token_assemble / pos_assemble, the loss through the fused patch kernels."""
-        neighborhood, center, _ = self.group_divider(pts)
+    def _rebuild(self, neighborhood, center, mask_noise=None, mask_start=None, mask=None, chosen=None):
+        """select -> encoder on the visible tokens -> decoder -> point head.
+        -> (mask, vis_ids, mask_ids, pred (B,M,3k), chosen).  chosen: the replayable path (see forward); None: decided by the arguments."""
         enc = self.MAE_encoder
-        if noaug:
-            return enc(neighborhood, center, noaug=True)[0]
-        chosen = mask is not None or mask_noise is not None or mask_start is not None or enc.device_mask
+        if chosen is None:
+            chosen = mask is not None or mask_noise is not None or mask_start is not None or enc.device_mask
         mask, vis_ids, mask_ids, _ = enc.select(center, False, mask_noise, mask_start, mask)
         B, N = mask_ids.shape
         tokens = enc.encoder(neighborhood)
         pos = _pos_mlp(enc.pos_embed, center)
         dpos = _pos_mlp(self.decoder_pos_embed, center)
-        if chosen and M.FUSED_HEADS and pts.is_cuda:
+        if chosen and M.FUSED_HEADS and center.is_cuda:
             from . import heads
             tok_vis, pos_vis, _ = heads.token_assemble(tokens, pos, vis_ids, mask_ids)
             _, pos_full = heads.pos_assemble(dpos, vis_ids, mask_ids, dt=tok_vis.dtype)
@@ -156,15 +153,40 @@ class Point_MAE(nn.Module):
         x_rec = self.MAE_decoder(x_full, pos_full, N)[:, -N:]          # P/:212: only the masked tokens are decoded to points
         pred = self._points(x_rec)
         if chosen and M.FUSED_HEADS:
-            from . import heads
             pred = pred.contiguous()
+        return mask, vis_ids, mask_ids, pred, chosen
+
+    def _patch_loss(self, pred, neighborhood, mask_ids, chosen):
+        """-> (the loss of P/:425-426, its per-patch values (B,M) when the fused patch kernel formed them, else None)."""
+        B, N = mask_ids.shape
+        if chosen and M.FUSED_HEADS:
+            from . import heads
             if heads.patch_chamfer_loss_supported(pred, neighborhood, mask_ids):
                 # cdl2: mean(d1) + mean(d2) over equal-sized patches = the mean of the per-point d1 + d2 the GM3D loss kernel forms
                 fn = heads.PatchChamferLossFn if self.loss == "cdl2" else heads.PatchChamferL1LossFn
-                return fn.apply(pred, neighborhood, mask_ids)[0]
+                return fn.apply(pred, neighborhood, mask_ids)
         rebuild = pred.reshape(B * N, -1, 3).float()
         gt = take(neighborhood, mask_ids).reshape(B * N, -1, 3)
-        return self.loss_func(rebuild, gt)
+        return self.loss_func(rebuild, gt), None
+
+    def forward(self, pts, noaug=False, vis=False, mask_noise=None, mask_start=None, mask=None, **kwargs):
+        """P/:391-441 (Point-MAE pre-training loss).  mask / mask_noise / mask_start: see MaskTransformer.select.  With any of them
+        (or MAE_encoder.device_mask) on a GPU the step is the replayable one: token and position gathers through
+        heads.token_assemble / pos_assemble, the loss through the fused patch kernels.
+        vis=True (P/:428-439): no loss; -> (ret1 (1,B*G*k,3): all clouds' visible patches then all rebuilt ones, back at their centres,
+        ret2 (1,B*V*k,3): the visible part, a view of ret1's head, full_center (B*G,3): all masked centres then all visible ones),
+        assembled by ops.reconstruct_assemble(flat=True) for any B and returned detached: the launch has no backward."""
+        neighborhood, center, _ = self.group_divider(pts)
+        if noaug:
+            return self.MAE_encoder(neighborhood, center, noaug=True)[0]
+        mask, vis_ids, mask_ids, pred, chosen = self._rebuild(neighborhood, center, mask_noise, mask_start, mask)
+        if vis:
+            from . import ops
+            p = pred if pred.stride(1) == pred.shape[2] and pred.stride(2) == 1 else pred.contiguous()
+            dense, full_center = ops.reconstruct_assemble(p, neighborhood, center, vis_ids, mask_ids, flat=True)
+            ret1 = dense.unsqueeze(0)
+            return ret1, ret1[:, :pts.shape[0] * vis_ids.shape[1] * self.group_size], full_center
+        return self._patch_loss(pred, neighborhood, mask_ids, chosen)[0]
 
     @torch.no_grad()
     def features_decoder(self, neighborhood, center, features, mask_ids):

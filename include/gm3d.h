@@ -904,6 +904,31 @@ int gm3d_linprobe_eval(const float *Q, const long long *yq, int m, int d, int nc
                        const float *running_mean, const float *running_var, float *logits, long long *pred, long long *correct,
                        gm3d_stream_t stream);
 
+/* ---- Reconstructed clouds (gm3d_amd/csrc/reconstruct.hip) -----------------------------------------------------------------------------
+ * The `vis` branch of Point-MAE_SA3D/models/Point_MAE.py:428-439 in one launch: the visible patches moved back to their centres, the
+ * decoder's patches placed at the masked centres, and the centres in matching order.
+ * pred (B,M,3k) f32 or bf16 (dtype), batch stride pred_bstride in elements (the last-M view of a (B,L,3k) tensor is taken as it is;
+ * rows are dense); neighborhood (B,G,k,3) f32, centre-relative; center (B,G,3) f32; vis_ids (B,V) and mask_ids (B,M) int64 with row
+ * strides vis_stride / mask_stride in elements.  The ids are trusted, like gm3d_token_assemble_fwd's (one outside 0..G-1 is clamped
+ * into that range, so no read leaves its cloud).  dense (B*G*k,3) f32 and full_center (B*G,3) f32: every element is written.
+ *   visible row  = neighborhood[b, id, j] + center[b, id]                      (one fp32 add)
+ *   rebuilt row  = float(pred[b, m, 3j .. 3j+2]) + center[b, mask_ids[b, m]]   (one fp32 add)
+ * layout GM3D_RECON_PER_CLOUD: patch block b*G + i of dense is cloud b's [visible patches in vis_ids order | rebuilt patches in
+ *   mask_ids order]; full_center has the same order, so centre i belongs to rows i*k .. i*k + k - 1.
+ * layout GM3D_RECON_FLAT (the reference's, for any B): all clouds' visible patches (block b*V + i), then all clouds' rebuilt patches
+ *   (B*V + b*M + i); full_center is all MASKED centres (row b*M + i), then all visible ones (B*M + b*V + i) -- the reference's own
+ *   disagreement between its two outputs, kept.
+ * Limits, checked on the host before any launch: GM3D_EINVAL for a NULL neighborhood / center / dense / full_center, B < 0, G < 1,
+ * k < 1, V < 0, M < 0, V + M != G, an unknown layout or dtype, a NULL vis_ids or vis_stride < V when V > 0, a NULL mask_ids / pred,
+ * mask_stride < M or pred_bstride < M*3k when M > 0 (with V == 0 or M == 0 the matching pointers may be NULL);
+ * GM3D_EUNSUPPORTED for B*G*k*3 >= 2^31.  B == 0 returns GM3D_OK without a launch.
+ * One wave per patch, 16-byte accesses when k % 4 == 0 and the bases are aligned, 4-byte ones otherwise; no LDS. */
+enum { GM3D_RECON_PER_CLOUD = 0, GM3D_RECON_FLAT = 1 };
+int gm3d_reconstruct_assemble(const void *pred, long long pred_bstride, const float *neighborhood, const float *center,
+                              const long long *vis_ids, long long vis_stride, const long long *mask_ids, long long mask_stride,
+                              int B, int G, int k, int V, int M, int layout, float *dense, float *full_center, int dtype,
+                              gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
