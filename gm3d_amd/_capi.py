@@ -162,6 +162,7 @@ SIGNATURES = {
     "gm3d_linprobe_eval": [_vp, _vp, _i, _i, _i] + [_vp] * 7 + [_vp],
     "gm3d_reconstruct_assemble": [_vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _i, _i, _i, _i, _i,
                                   _i, _vp, _vp, _i, _vp],
+    "gm3d_reconstruct_partition": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
 }
 
 

@@ -8,6 +8,16 @@
 // aligned bases: the VEC instantiation), 4 bytes each otherwise.  A visible row is neighborhood + centre, a rebuilt row
 // float(pred) + centre: one fp32 add per element and nothing else, so the result is the aten chain's, bit for bit.
 // No LDS, no barriers, no atomics; every element of both outputs is written exactly once.
+//
+// gm3d_reconstruct_partition is the ragged form for the hierarchical model, where the visible count differs from cloud to cloud: the
+// id lists are replaced by the mask bytes, and the launch itself forms the stable partition [visible tokens | masked tokens] of every
+// cloud.  ceil(G/16) workgroups per cloud; each recomputes the cloud's ranks from the G mask bytes -- one 64-bit ballot and popcount per
+// 64-token chunk, an exclusive prefix over the (at most 128) chunk counts in LDS -- which is cheaper than a second launch or a
+// grid-wide wait, and then moves its 16 tokens at once: 16 lanes per patch, four patches per wave -- the model's patches are 6 (k = 8)
+// and 12 (k = 16) 16-byte units, so a whole wave per patch leaves most lanes idle and makes a wave walk its patches one dependent
+// read chain after the other (measured: DESIGN 16).  The workgroup walks TOKENS, not slots: a token's slot is `visible tokens before
+// it` or `all visible + masked tokens before it`, so no inverse map is needed and the slots, being a permutation, are still written
+// exactly once.  No atomics, no dependence between workgroups.
 #include "common.hpp"
 
 namespace gm3d {
@@ -26,12 +36,12 @@ template <> __device__ __forceinline__ void ra_load4<bf16_t>(const bf16_t* p, fl
     for (int i = 0; i < 4; ++i) v[i] = (float)a[i];
 }
 
-// Elements [0, row) of one patch: out[e] = float(src[e]) + c[e % 3].
-template <class S, bool VEC>
+// Elements [0, row) of one patch, by the LANES lanes `lane` = 0 .. LANES-1: out[e] = float(src[e]) + c[e % 3].
+template <class S, bool VEC, int LANES = GM3D_WAVE>
 __device__ __forceinline__ void ra_patch(const S* __restrict__ src, float* __restrict__ out, int row, int lane, float cx, float cy,
                                          float cz) {
     if (VEC) {
-        for (int q = lane; q < (row >> 2); q += GM3D_WAVE) {
+        for (int q = lane; q < (row >> 2); q += LANES) {
             float v[4];
             ra_load4<S>(src + 4 * q, v);
             const int r = q % 3;                             // element 4q + t is coordinate (q + t) % 3
@@ -41,7 +51,7 @@ __device__ __forceinline__ void ra_patch(const S* __restrict__ src, float* __res
                 make_float4(__fadd_rn(v[0], c0), __fadd_rn(v[1], c1), __fadd_rn(v[2], c2), __fadd_rn(v[3], c0));
         }
     } else {
-        for (int e = lane; e < row; e += GM3D_WAVE) {
+        for (int e = lane; e < row; e += LANES) {
             const int r = e % 3;
             out[e] = __fadd_rn((float)src[e], r == 0 ? cx : (r == 1 ? cy : cz));
         }
@@ -98,6 +108,72 @@ static void ra_launch(const void* pred, long long pred_bstride, const float* nei
                        V, M, layout, dense, full_center);
 }
 
+constexpr int RP_WAVES = 4, RP_LANES = 16, RP_TOKENS = RP_WAVES * GM3D_WAVE / RP_LANES, RP_MAX_G = 8192,
+              RP_MAX_CHUNKS = RP_MAX_G / GM3D_WAVE;
+
+// PRED == false: no decoder output; a masked token's rows are its true patch (T is float and `pred` is not read).
+template <class T, bool VEC, bool PRED>
+__global__ __launch_bounds__(RP_WAVES* GM3D_WAVE) void reconstruct_partition_kernel(
+    const T* __restrict__ pred, const float* __restrict__ neighborhood, const float* __restrict__ center,
+    const unsigned char* __restrict__ masked, int G, int k, int slices, float* __restrict__ dense, float* __restrict__ full_center,
+    int* __restrict__ order, int* __restrict__ n_visible) {
+    __shared__ unsigned long long s_vis[RP_MAX_CHUNKS];      // bit l of entry c: token 64c + l is visible
+    __shared__ int s_before[RP_MAX_CHUNKS + 1];              // visible tokens in the chunks before c; the last used entry: all of them
+    const int lane = threadIdx.x & (GM3D_WAVE - 1), wave = threadIdx.x / GM3D_WAVE;
+    const int b = blockIdx.x / slices, slice = blockIdx.x - b * slices;
+    const int chunks = (G + GM3D_WAVE - 1) / GM3D_WAVE, row = 3 * k;
+    const unsigned char* m = masked + (size_t)b * G;
+    for (int c = wave; c < chunks; c += RP_WAVES) {
+        const int t = c * GM3D_WAVE + lane;
+        const unsigned long long vis = __ballot(t < G && m[t] == 0);
+        if (lane == 0) s_vis[c] = vis;
+    }
+    __syncthreads();
+    if (wave == 0) {                                         // exclusive prefix of the chunk counts: two chunks per lane
+        const int c0 = 2 * lane, c1 = c0 + 1;
+        const int n0 = c0 < chunks ? __popcll(s_vis[c0]) : 0, n1 = c1 < chunks ? __popcll(s_vis[c1]) : 0;
+        int incl = n0 + n1;
+#pragma unroll
+        for (int d = 1; d < GM3D_WAVE; d <<= 1) {
+            const int up = __shfl_up(incl, d, GM3D_WAVE);
+            if (lane >= d) incl += up;
+        }
+        const int excl = incl - (n0 + n1);
+        if (c0 < chunks) s_before[c0] = excl;
+        if (c1 < chunks) s_before[c1] = excl + n0;
+        if (lane == GM3D_WAVE - 1) s_before[chunks] = incl;
+    }
+    __syncthreads();
+    const int nv = s_before[chunks];
+    if (slice == 0 && threadIdx.x == 0) n_visible[b] = nv;
+    const int t = slice * RP_TOKENS + threadIdx.x / RP_LANES, sub = lane & (RP_LANES - 1);      // 16 lanes share a token
+    if (t < G) {
+        const int c = t / GM3D_WAVE, l = t & (GM3D_WAVE - 1);
+        const unsigned long long vis = s_vis[c];
+        const int before = s_before[c] + __popcll(vis & ((1ull << l) - 1));      // visible tokens in front of t
+        const bool is_masked = !((vis >> l) & 1);
+        const int slot = is_masked ? nv + (t - before) : before;
+        const size_t tok = (size_t)b * G + t, dst = (size_t)b * G + slot;
+        const float* cp = center + tok * 3;
+        const float cx = cp[0], cy = cp[1], cz = cp[2];
+        if (sub < 3) full_center[dst * 3 + sub] = sub == 0 ? cx : (sub == 1 ? cy : cz);
+        if (sub == 3) order[dst] = t;
+        float* out = dense + dst * row;
+        if (PRED && is_masked)
+            ra_patch<T, VEC, RP_LANES>(pred + tok * row, out, row, sub, cx, cy, cz);
+        else
+            ra_patch<float, VEC, RP_LANES>(neighborhood + tok * row, out, row, sub, cx, cy, cz);
+    }
+}
+
+template <class T, bool VEC, bool PRED>
+static void rp_launch(const void* pred, const float* neighborhood, const float* center, const unsigned char* masked, int B, int G, int k,
+                      float* dense, float* full_center, int* order, int* n_visible, hipStream_t st) {
+    const int slices = (G + RP_TOKENS - 1) / RP_TOKENS;      // B * slices <= B * G < 2^31 / 3: a valid grid
+    hipLaunchKernelGGL((reconstruct_partition_kernel<T, VEC, PRED>), dim3((unsigned)B * slices), dim3(RP_WAVES * GM3D_WAVE), 0, st,
+                       (const T*)pred, neighborhood, center, masked, G, k, slices, dense, full_center, order, n_visible);
+}
+
 }  // namespace gm3d
 
 extern "C" int gm3d_reconstruct_assemble(const void* pred, long long pred_bstride, const float* neighborhood, const float* center,
@@ -127,6 +203,34 @@ extern "C" int gm3d_reconstruct_assemble(const void* pred, long long pred_bstrid
         if (vec) GM3D_RA(float, true); else GM3D_RA(float, false);
     }
 #undef GM3D_RA
+    GM3D_CHECK_LAUNCH();
+    return GM3D_OK;
+}
+
+extern "C" int gm3d_reconstruct_partition(const void* pred, const float* neighborhood, const float* center, const unsigned char* masked,
+                                          int B, int G, int k, int dtype, float* dense, float* full_center, int* order, int* n_visible,
+                                          gm3d_stream_t stream) {
+    using namespace gm3d;
+    if (!neighborhood || !center || !masked || !dense || !full_center || !order || !n_visible) return GM3D_EINVAL;
+    if (B < 0 || G < 1 || k < 1) return GM3D_EINVAL;
+    if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
+    if (G > RP_MAX_G) return GM3D_EUNSUPPORTED;                                   // the chunk prefix is one wave, two chunks per lane
+    if ((long long)B * G * k * 3 >= 0x80000000LL) return GM3D_EUNSUPPORTED;      // the grid size and the row length are ints
+    if (B == 0) return GM3D_OK;
+    const size_t esz = dtype == GM3D_BF16 ? 2 : 4;
+    // 16-byte accesses need 16-byte patch rows everywhere: k % 4 == 0 and aligned bases (pred rows are dense: 3k elements)
+    const bool vec = k % 4 == 0 && ((uintptr_t)neighborhood | (uintptr_t)dense) % 16 == 0 && (!pred || (uintptr_t)pred % (4 * esz) == 0);
+    hipStream_t st = (hipStream_t)stream;
+#define GM3D_RP(T, VEC, PRED) \
+    rp_launch<T, VEC, PRED>(pred, neighborhood, center, masked, B, G, k, dense, full_center, order, n_visible, st)
+    if (!pred) {
+        if (vec) GM3D_RP(float, true, false); else GM3D_RP(float, false, false);
+    } else if (dtype == GM3D_BF16) {
+        if (vec) GM3D_RP(bf16_t, true, true); else GM3D_RP(bf16_t, false, true);
+    } else {
+        if (vec) GM3D_RP(float, true, true); else GM3D_RP(float, false, true);
+    }
+#undef GM3D_RP
     GM3D_CHECK_LAUNCH();
     return GM3D_OK;
 }

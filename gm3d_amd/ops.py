@@ -636,3 +636,42 @@ def reconstruct_assemble(pred, neighborhood, center, vis_ids, mask_ids, flat=Fal
             _ptr(vis_ids) if V > 0 else None, bstride(vis_ids, V) if V > 0 else 0, _ptr(mask_ids) if M > 0 else None,
             bstride(mask_ids, M) if M > 0 else 0, B, G, k, V, M, 1 if flat else 0, _ptr(dense), _ptr(full_center), dt, _stream())
     return dense, full_center
+
+
+@torch.no_grad()
+def reconstruct_partition(pred, neighborhood, center, masked):
+    """The ragged form for the hierarchical model, one launch (gm3d_reconstruct_partition): a stable per-cloud partition of the tokens
+    by `masked` (B,G) bool or uint8 (non-zero = masked) with the patches moved back to their centres in that order.  neighborhood
+    (B,G,k,3) f32 centre-relative, center (B,G,3) f32; pred (B,G,3k) f32/bf16 contiguous with a row for EVERY token (rows of visible
+    tokens are never read), or None: a masked token's rows are then its true patch.
+    -> (dense (B,G*k,3) f32: per cloud [visible patches | masked patches], each in ascending token index; full_center (B,G,3) f32 and
+    order (B,G) int32 (the token at each slot) in the same order; n_visible (B,) int32), detached (there is no backward)."""
+    neighborhood, center = neighborhood.detach(), center.detach()
+    _require(neighborhood, torch.float32, "neighborhood")
+    _require(center, torch.float32, "center")
+    _require(masked, None, "masked")
+    if neighborhood.dim() != 4 or neighborhood.size(3) != 3 or tuple(center.shape) != tuple(neighborhood.shape[:2]) + (3,):
+        raise RuntimeError("neighborhood must be (B,G,k,3) and center (B,G,3)")
+    B, G, k, _ = neighborhood.shape
+    if masked.dtype not in (torch.bool, torch.uint8) or tuple(masked.shape) != (B, G):
+        raise RuntimeError("masked must be (B,G) = (%d,%d) bool or uint8" % (B, G))
+    dt = _capi.GM3D_F32
+    if pred is not None:
+        pred = pred.detach()
+        _require(pred, None, "pred")
+        if pred.dtype not in _DT:
+            raise RuntimeError("pred must be float32 or bfloat16")
+        if tuple(pred.shape) != (B, G, 3 * k):
+            raise RuntimeError("pred must be (B,G,3k) = (%d,%d,%d): a row for every token" % (B, G, 3 * k))
+        dt = _DT[pred.dtype]
+    dev = neighborhood.device
+    dense = torch.empty(B, G * k, 3, dtype=torch.float32, device=dev)
+    full_center = torch.empty(B, G, 3, dtype=torch.float32, device=dev)
+    order = torch.empty(B, G, dtype=torch.int32, device=dev)
+    n_visible = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return dense, full_center, order, n_visible
+    _launch("gm3d_reconstruct_partition", {"B": B, "G": G, "k": k, "pred": pred is not None}, lib.gm3d_reconstruct_partition,
+            _ptr(pred), _ptr(neighborhood), _ptr(center), _ptr(masked), B, G, k, dt, _ptr(dense), _ptr(full_center), _ptr(order),
+            _ptr(n_visible), _stream())
+    return dense, full_center, order, n_visible

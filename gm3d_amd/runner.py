@@ -5,6 +5,9 @@ Same category filter, folder name `{taxonomy_id}_{idx}` and np.savetxt(..., deli
 are accepted -- the model's flat vis=True layout is split per cloud, one folder each, `idx` the running cloud index over the loader
 (the reference's batch index at its batch size 1), the filter applied per batch entry --, and the rendered plot.jpg (matplotlib +
 OpenCV) is not produced: the reference's view angles of each category come back in the per-cloud record for whoever renders.
+
+test_m2ae is the same tester for Point-M2AE + GeoMask3D (reconstruct.reconstruct_m2ae): vis.txt holds the cloud's visible level-0
+points -- the raw input points the encoder saw, a different number of rows per cloud -- and dense_points.txt its dense level-1 cloud.
 """
 import os
 
@@ -71,6 +74,38 @@ def test(base_model, test_dataloader, out_dir="./vis", useful_cate=USEFUL_CATE, 
             os.makedirs(data_path, exist_ok=True)
             np.savetxt(os.path.join(data_path, "gt.txt"), gt[b], delimiter=";")
             np.savetxt(os.path.join(data_path, "vis.txt"), vis[b], delimiter=";")
+            np.savetxt(os.path.join(data_path, "dense_points.txt"), dense[b], delimiter=";")
+            records.append({"idx": first + b, "taxonomy_id": taxonomy_ids[b], "model_id": model_ids[b], "path": data_path,
+                            "view": VIEW_ANGLES.get(taxonomy_ids[b], (0, 0))})
+            if first + b > max_idx:
+                return records
+    return records
+
+
+@torch.no_grad()
+def test_m2ae(model, teacher, test_dataloader, out_dir, epoch, total_epoch, useful_cate=USEFUL_CATE, max_idx=1500, bf16=False):
+    """`test` for the hierarchical model: the student `model` and its EMA `teacher` (module or ModelEma; None is refused by
+    reconstruct_m2ae, which then needs a mask) through reconstruct.reconstruct_m2ae(model, points, teacher, epoch, total_epoch) per
+    kept batch.  Same loader triple, category filter per batch entry, running idx, folder names, files and records as `test`."""
+    from . import reconstruct
+    dev = _device_of(model)
+    records, idx = [], 0
+    for taxonomy_ids, model_ids, data in test_dataloader:
+        B = data.shape[0]
+        keep = [b for b in range(B) if taxonomy_ids[b] in useful_cate]
+        first, idx = idx, idx + B
+        if not keep:
+            continue
+        points = data if dev is None else data.to(dev)
+        r = reconstruct.reconstruct_m2ae(model, points, teacher, epoch, total_epoch, bf16=bf16)
+        k0 = r.points0.shape[1] // r.masks[0].shape[1]
+        rows0 = (r.n_visible0.cpu().numpy().astype(np.int64) * k0).tolist()       # the one read of the ragged counts, outside the pass
+        gt, dense, points0 = points.detach().cpu().numpy(), r.dense.float().cpu().numpy(), r.points0.float().cpu().numpy()
+        for b in keep:
+            data_path = os.path.join(out_dir, "%s_%d" % (taxonomy_ids[b], first + b))
+            os.makedirs(data_path, exist_ok=True)
+            np.savetxt(os.path.join(data_path, "gt.txt"), gt[b], delimiter=";")
+            np.savetxt(os.path.join(data_path, "vis.txt"), points0[b, :rows0[b]], delimiter=";")
             np.savetxt(os.path.join(data_path, "dense_points.txt"), dense[b], delimiter=";")
             records.append({"idx": first + b, "taxonomy_id": taxonomy_ids[b], "model_id": model_ids[b], "path": data_path,
                             "view": VIEW_ANGLES.get(taxonomy_ids[b], (0, 0))})

@@ -928,6 +928,26 @@ int gm3d_reconstruct_assemble(const void *pred, long long pred_bstride, const fl
                               const long long *vis_ids, long long vis_stride, const long long *mask_ids, long long mask_stride,
                               int B, int G, int k, int V, int M, int layout, float *dense, float *full_center, int dtype,
                               gm3d_stream_t stream);
+/* The ragged form, for the hierarchical model (gm3d_amd/point_m2ae.py), whose visible count at the finer levels differs from cloud
+ * to cloud: a stable per-cloud partition of the G tokens by `masked` (B,G) bytes (non-zero = masked, gm3d_partition_visible's sense)
+ * with the patches moved back to their centres in that order, in one launch.  Slot order of cloud b: its visible tokens in ascending
+ * token index, then its masked tokens in ascending token index; order (B,G) int32 = the token at each slot, n_visible (B) int32 = the
+ * number of visible tokens.  neighborhood (B,G,k,3) f32, centre-relative; center (B,G,3) f32; pred (B,G,3k) f32 or bf16 (dtype),
+ * contiguous, a row for EVERY token -- rows of visible tokens are never read --, or NULL: a masked token's rows are then its true patch
+ * (dense = [visible patches | hidden ground truth]).  dense (B*G*k,3) f32, full_center (B*G,3) f32, order and n_visible: every
+ * element is written exactly once.
+ *   visible token t at slot s:  dense[b, s, j] = neighborhood[b, t, j] + center[b, t]                    (one fp32 add)
+ *   masked token t at slot s:   dense[b, s, j] = float(pred[b, t, 3j .. 3j+2]) + center[b, t]            (one fp32 add)
+ *   full_center[b, s] = center[b, t]
+ * Limits, checked on the host before any launch: GM3D_EINVAL for a NULL neighborhood / center / masked / dense / full_center / order /
+ * n_visible, B < 0, G < 1, k < 1 or an unknown dtype (also with pred NULL); GM3D_EUNSUPPORTED for G > 8192 or B*G*k*3 >= 2^31.
+ * B == 0 returns GM3D_OK without a launch.
+ * ceil(G/16) workgroups per cloud; each recomputes its cloud's ranks from the G mask bytes (64-bit ballots, popcounts, a prefix over
+ * the 64-token chunks in LDS) and moves 16 tokens at once, 16 lanes per patch, with 16-byte accesses when k % 4 == 0 and the bases are
+ * aligned and 4-byte ones otherwise.  No atomics, no dependence between workgroups. */
+int gm3d_reconstruct_partition(const void *pred, const float *neighborhood, const float *center, const unsigned char *masked, int B,
+                               int G, int k, int dtype, float *dense, float *full_center, int *order, int *n_visible,
+                               gm3d_stream_t stream);
 
 #ifdef __cplusplus
 }
