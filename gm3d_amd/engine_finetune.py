@@ -153,38 +153,25 @@ class GraphedFinetuneStep:
         self.points = example_points.clone()
         self.targets = example_targets.clone()
         self.subset = torch.zeros(npoints, dtype=torch.long, device=example_points.device)
-        self._pin = [torch.empty(npoints, dtype=torch.long).pin_memory() for _ in range(2)]
-        self._pin_ev, self._pin_i = [None, None], 0
+        self._feed = streams.PinnedFeed(self.subset)
         self.overlap = bool(overlap_sampling)
         self._draw()
         if self.overlap:
-            B = example_points.size(0)
-            self.staged = torch.zeros(B, npoints, 3, dtype=torch.float32, device=example_points.device)
-            self.pts = torch.zeros_like(self.staged)
-            self.pts.copy_(sample_points(self.points, npoints, subset=self.subset))
-            self.sstream = torch.cuda.Stream()
-            self._ready, self._staged = torch.cuda.Event(), False
+            self.pts = sample_points(self.points, npoints, subset=self.subset)
+            self.staged = torch.zeros_like(self.pts)
+            self.stage = streams.SideStage(example_points.device)
         streams.warm_up(self._body, warmup_iters)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with streams.capture(self.graph):
             self.out = self._body()
-        if self.overlap:
-            self.sample_graph = torch.cuda.CUDAGraph()
-            with streams.capture(self.sample_graph, stream=self.sstream):
-                self.staged.copy_(sample_points(self.points, npoints, subset=self.subset))
+        if self.overlap:          # the sampler stream's graph: clouds + subset -> FPS + gather -> self.staged
+            self.stage.capture(lambda: self.staged.copy_(sample_points(self.points, npoints, subset=self.subset)))
             torch.cuda.synchronize()
 
     def _draw(self):
-        """Host draw of the shared FPS subset -> device, through two alternating pinned buffers so that the copy is
-        asynchronous (a pageable copy would make the host wait for everything queued before it, once per step)."""
-        i, self._pin_i = self._pin_i, self._pin_i ^ 1
-        if self._pin_ev[i] is not None:
-            self._pin_ev[i].synchronize()
-        self._pin[i].copy_(torch.from_numpy(self.rng.choice(self.point_all, self.npoints, False).astype(np.int64)))
-        self.subset.copy_(self._pin[i], non_blocking=True)
-        self._pin_ev[i] = torch.cuda.Event()
-        self._pin_ev[i].record(torch.cuda.current_stream())
+        """Host draw of the shared FPS subset -> device, on the current stream."""
+        self._feed.push([self.rng.choice(self.point_all, self.npoints, False).astype(np.int64)])
 
     def _body(self):
         if self.overlap:
@@ -193,20 +180,6 @@ class GraphedFinetuneStep:
         return finetune_step(self.model, self.criterion, self.opt, self.points, self.targets, npoints=self.npoints,
                              max_norm=self.max_norm, bf16=self.bf16, subset=self.subset, augment=self.augment)
 
-    def _enqueue_sampling(self, points):
-        """Sampler stream: (after everything the caller's stream has queued so far -- the producer of `points`, and the copy that
-        consumed the previous staged batch) clouds in, subset draw, FPS + gather graph -> self.staged."""
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        with torch.cuda.stream(self.sstream):
-            self.sstream.wait_event(ev)
-            self.points.copy_(points, non_blocking=True)
-            points.record_stream(self.sstream)
-            self._draw()
-            self.sample_graph.replay()
-            self._ready.record(self.sstream)
-        self._staged = True
-
     def __call__(self, points, targets, next_points=None):
         if not self.overlap:
             self.points.copy_(points, non_blocking=True)
@@ -214,15 +187,12 @@ class GraphedFinetuneStep:
             self._draw()
             self.graph.replay()
             return self.out
-        main = torch.cuda.current_stream()
-        if not self._staged:                      # first call (or no look-ahead given last time): sample this batch now
-            self._enqueue_sampling(points)
-        main.wait_event(self._ready)
+        # the subset is drawn on the sampler stream, between the clouds' copy and the sampling graph that reads it
+        self.stage.take(points, self.points, before_replay=self._draw)
         self.pts.copy_(self.staged)
         self.targets.copy_(targets, non_blocking=True)
-        self._staged = False
         if next_points is not None:               # queued BEFORE the training graph so that the two run side by side
-            self._enqueue_sampling(next_points)
+            self.stage.enqueue(next_points, self.points, before_replay=self._draw)
         self.graph.replay()
         return self.out
 
@@ -242,21 +212,14 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     n_iter = len(data_loader)
     seen, loss_sum, last = 0, 0.0, None
 
-    def batches():          # (it, points, targets, next batch's points or None), everything already on the device
-        prev = None
-        for it, (_taxonomy_ids, _model_ids, data) in enumerate(data_loader):
-            cur = (it, data[0].to(device, non_blocking=True), data[1].to(device, non_blocking=True))
-            if prev is not None:
-                yield prev + (cur[1],)
-            prev = cur
-        if prev is not None:
-            yield prev + (None,)
-
-    for it, points, targets, nxt in batches():
+    # (taxonomy, model_id, (points, label)) -> (points, targets) on the device, the next batch's while the current one trains
+    loader = streams.LookAhead(data_loader, lambda item: tuple(t.to(device, non_blocking=True) for t in item[2][:2]))
+    for it, (points, targets) in enumerate(loader):
         if it % accum_iter == 0:
             adjust_learning_rate(optimizer, it / n_iter + epoch, args)
         if step is not None and points.shape == step.points.shape:
             if step.overlap:
+                nxt = None if loader.next is None else loader.next[0]
                 out = step(points, targets, next_points=nxt if nxt is not None and nxt.shape == points.shape else None)
             else:
                 out = step(points, targets)
@@ -353,28 +316,18 @@ def draw_votes(rng, point_all, npoints, times, B):
 
 
 class _VoteDraws:
-    """Device copies of one batch's draws, staged through two alternating pinned buffers (asynchronous copies, like
-    GraphedFinetuneStep._draw).  Before the first stage() they hold a draw-free warm-up value (identity transform)."""
+    """Device copies of one batch's draws, staged through a streams.PinnedFeed (asynchronous copies, like the fine-tune step's
+    subset).  Before the first stage() they hold a draw-free warm-up value (identity transform)."""
 
     def __init__(self, times, npoints, B, device):
         self.times, self.npoints, self.B = times, npoints, B
         self.subsets = torch.arange(npoints, dtype=torch.long, device=device).repeat(times, 1)
         self.scale = torch.ones(times, B, 3, dtype=torch.float32, device=device)
         self.shift = torch.zeros(times, B, 3, dtype=torch.float32, device=device)
-        self._pin = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in (self.subsets, self.scale, self.shift))
-                     for _ in range(2)]
-        self._ev, self._i = [None, None], 0
+        self._feed = streams.PinnedFeed(self.subsets, self.scale, self.shift)
 
     def stage(self, rng, point_all):
-        drawn = draw_votes(rng, point_all, self.npoints, self.times, self.B)
-        i, self._i = self._i, self._i ^ 1
-        if self._ev[i] is not None:
-            self._ev[i].synchronize()
-        for pin, dev, arr in zip(self._pin[i], (self.subsets, self.scale, self.shift), drawn):
-            pin.copy_(torch.from_numpy(arr))
-            dev.copy_(pin, non_blocking=True)
-        self._ev[i] = torch.cuda.Event()
-        self._ev[i].record(torch.cuda.current_stream())
+        self._feed.push(draw_votes(rng, point_all, self.npoints, self.times, self.B))
 
 
 def vote_batch(model, points, labels, subsets, scale, shift, point_all, correct, bf16=True, max_clouds=None, votes=None):

@@ -550,20 +550,17 @@ class GraphedPretrainStep:
             streams.warm_up(lambda: whole(self.static_in.clone()), warmup_iters)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        # with a process group alive its watchdog thread polls events; only the capturing thread's calls may abort a capture
-        import os
-        mode = "thread_local" if dist.is_initialized() else "global"
         if not two:
             self.graph2 = None
-            with streams.capture(self.graph, capture_error_mode=mode):
+            with streams.capture(self.graph):
                 self.out = whole(self.static_in)
         else:
-            with streams.capture(self.graph, capture_error_mode=mode):
+            with streams.capture(self.graph):
                 self.out = fwd_bwd(model, model_ema, self.static_in, epoch, args, optimizer=optimizer, **kw)
             self.graph2 = torch.cuda.CUDAGraph()
             if hasattr(optimizer, "mark_grads_filled"):
                 optimizer.mark_grads_filled()       # G is complete when this graph runs (gathered / collected / all-reduced)
-            with streams.capture(self.graph2, pool=self.graph.pool(), capture_error_mode=mode):
+            with streams.capture(self.graph2, pool=self.graph.pool()):
                 self.out["grad_norm"] = step_update(model, model_ema, optimizer)
 
     def _collect(self):

@@ -19,6 +19,7 @@ import torch.distributed as dist
 
 from . import engine_pretrain as E
 from . import point_m2ae as P
+from . import streams
 
 _generators = weakref.WeakKeyDictionary()   # model -> its augmentation generator (kept across epochs: fresh draws every epoch)
 
@@ -57,27 +58,6 @@ def augment_generator(model, device, args):
         g.manual_seed(int(getattr(args, "seed", 0)) + rank)
         _generators[model] = g
     return g
-
-
-class _LookAhead:
-    """The loader's batches on `device`, one batch ahead: while batch i is trained, `next` is batch i + 1 (None at the end)."""
-
-    def __init__(self, loader, device):
-        self.loader, self.device, self.next = loader, device, None
-
-    def __len__(self):
-        return len(self.loader)
-
-    def __iter__(self):
-        it = iter(self.loader)
-        cur = next(it, None)
-        cur = None if cur is None else cur.to(self.device, non_blocking=True)
-        while cur is not None:
-            nxt = next(it, None)
-            self.next = None if nxt is None else nxt.to(self.device, non_blocking=True)
-            yield cur
-            cur = self.next
-        self.next = None
 
 
 def _as_run_epoch_out(out, device):
@@ -131,7 +111,7 @@ def train_one_epoch(model, data_loader, optimizer, device, epoch, loss_scaler=No
     if device.type == "cuda":
         from . import masked_stack
         masked_stack.overflow_flag(device).zero_()       # this epoch's overflow only (the kernels never clear it)
-    loader = _LookAhead(data_loader, device)
+    loader = streams.LookAhead(data_loader, lambda batch: batch.to(device, non_blocking=True))
     if world > 1 and not getattr(optimizer, "_m2ae_broadcast", False):
         # DDP's constructor: rank 0's parameters, optimizer state, teacher and buffers (the ranks were seeded differently)
         E.broadcast_state(model, model_ema, optimizer)

@@ -20,6 +20,7 @@ from types import SimpleNamespace
 import torch
 
 from . import engine_pretrain as E
+from . import streams
 from .engine_pretrain import train_transforms  # noqa: F401 (part of this module's interface, like the sibling engines)
 
 
@@ -157,7 +158,6 @@ def train_one_epoch(model, data_loader, optimizer, device, epoch, args, log_writ
     run eagerly, then the step is captured once and replayed, the next batch being copied to the device while the current one
     trains; a batch of another shape (a smaller last batch) runs eagerly.  The finite-loss guard is a device flag read every
     print_freq iterations and at the end.  use_graph=False (or a torch optimizer) keeps every iteration eager."""
-    from .engine_pretrain_m2ae import _LookAhead
     device = torch.device(device)
     raw = model.module if hasattr(model, "module") else model
     raw.MAE_encoder.device_mask = True
@@ -170,7 +170,7 @@ def train_one_epoch(model, data_loader, optimizer, device, epoch, args, log_writ
     if getattr(optimizer, "GA", None) is not None:      # a window the previous epoch left unfinished is discarded (num_iter = 0, P/tools/:117)
         optimizer.GA.zero_()
     optimizer.zero_grad()
-    loader = _LookAhead(data_loader, device)
+    loader = streams.LookAhead(data_loader, lambda batch: batch.to(device, non_blocking=True))
     n_iter = len(loader)
     losses = torch.zeros(max(n_iter, 1), dtype=torch.float32, device=device)
     graphed = _steps.get(model) if use_graph else None

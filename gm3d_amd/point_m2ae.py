@@ -590,8 +590,8 @@ class GraphedM2AEStep:
     Two graphs: `group_graph` = group_stage (augmentation, three FPS + KNN levels, 3-NN lists: ~1.3 ms of one-workgroup-per-cloud
     chains that use half the CUs and no parameter) on a second stream; `train_graph` = everything else (teacher, mask, student, losses,
     backward, clip + AdamW + EMA).  A call copies the staged results into the training graph's own inputs (one multi-tensor copy),
-    queues the next batch's grouping on the side stream and replays the training graph -- what engine_finetune.GraphedFinetuneStep does
-    for its point sampling.  Without `next_pts` the grouping of a batch runs right before its training (same results: the stages read
+    queues the next batch's grouping on the side stream and replays the training graph -- a streams.SideStage, like the one of
+    engine_finetune.GraphedFinetuneStep.  Without `next_pts` the grouping of a batch runs right before its training (same results: the stages read
     and write disjoint state; with augmentation on, the random draws of a batch are taken when its grouping is queued).
     `epoch` is baked into the captures (mask schedule), like GraphedPretrainStep.
     generator: a CUDA generator of its own for the augmentation draws, registered with `group_graph` only.  The two graphs replay on
@@ -624,18 +624,15 @@ class GraphedM2AEStep:
         dev = example.device
         self.static_in = example.clone()
         self.static_noise = torch.rand(example.shape[0], raw.num_group, device=dev) if inject_mask_noise else None
-        self.side = torch.cuda.Stream(device=dev)
-        self._ready, self._staged = torch.cuda.Event(), False
+        self.stage = streams.SideStage(dev)
 
     def _capture_grouping(self, divider):
         """capture `group_graph` on the side stream, replay it once (a capture executes nothing) -> the staged tuple the training
         capture reads (clones of the grouping outputs, refreshed by one multi-tensor copy per call)."""
-        self.group_graph = torch.cuda.CUDAGraph()
-        if self.generator is not None:
-            self.group_graph.register_generator_state(self.generator)
-        with streams.capture(self.group_graph, stream=self.side):
-            pts, group, prop = group_stage(divider, self.static_in, augment=self.augment, generator=self.generator)
-            self._stage_out = [pts] + list(group[0]) + list(group[1]) + list(group[2]) + list(prop)
+        pts, group, prop = self.stage.capture(
+            lambda: group_stage(divider, self.static_in, augment=self.augment, generator=self.generator), generator=self.generator)
+        self.group_graph = self.stage.graph
+        self._stage_out = [pts] + list(group[0]) + list(group[1]) + list(group[2]) + list(prop)
         torch.cuda.synchronize()
         self.group_graph.replay()            # real values for the capture below (a capture executes nothing)
         torch.cuda.synchronize()
@@ -644,29 +641,14 @@ class GraphedM2AEStep:
         ti = self._train_in
         return (ti[0], (ti[1:1 + n], ti[1 + n:1 + 2 * n], ti[1 + 2 * n:1 + 3 * n]), (ti[1 + 3 * n], ti[2 + 3 * n]))
 
-    def _enqueue_grouping(self, pts):
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())       # after the copy that consumed the previous staged batch, and after pts' producer
-        with torch.cuda.stream(self.side):
-            self.side.wait_event(ev)
-            self.static_in.copy_(pts, non_blocking=True)
-            pts.record_stream(self.side)
-            self.group_graph.replay()
-            self._ready.record(self.side)
-        self._staged = True
-
     def _take_staged(self, pts, mask_noise, next_pts):
         """this batch's grouping -> the training graph's inputs; the next batch's grouping queued on the side stream."""
-        main = torch.cuda.current_stream()
-        if not self._staged:                          # first call, or no look-ahead was given last time: group this batch now
-            self._enqueue_grouping(pts)
-        main.wait_event(self._ready)
+        self.stage.take(pts, self.static_in)
         torch._foreach_copy_(self._train_in, self._stage_out)
         if self.static_noise is not None and mask_noise is not None:
             self.static_noise.copy_(mask_noise, non_blocking=True)
-        self._staged = False
         if next_pts is not None:                      # queued BEFORE the training graph so that the two run side by side
-            self._enqueue_grouping(next_pts)
+            self.stage.enqueue(next_pts, self.static_in)
 
     def __call__(self, pts, mask_noise=None, next_pts=None):
         self._take_staged(pts, mask_noise, next_pts)

@@ -117,15 +117,13 @@ class SegmentedStep:
 
     def _capture(self, first_input):
         """NSEG + 1 graphs in one memory pool: a graph per segment (segment 0's returns the output dict), then clip + AdamW + EMA."""
-        # with a process group alive its watchdog thread polls events; only the capturing thread's calls may abort a capture
-        mode = "thread_local" if dist.is_initialized() else "global"
         self.graphs = [torch.cuda.CUDAGraph() for _ in range(self.NSEG + 1)]
-        with streams.capture(self.graphs[0], capture_error_mode=mode):
+        with streams.capture(self.graphs[0]):
             self.out = self._segment(0, first_input)
         for k in range(1, self.NSEG):
-            with streams.capture(self.graphs[k], pool=self.graphs[0].pool(), capture_error_mode=mode):
+            with streams.capture(self.graphs[k], pool=self.graphs[0].pool()):
                 self._segment(k)
-        with streams.capture(self.graphs[self.NSEG], pool=self.graphs[0].pool(), capture_error_mode=mode):
+        with streams.capture(self.graphs[self.NSEG], pool=self.graphs[0].pool()):
             self.out["grad_norm"] = self._update()
 
     def _store(self, seg, grads):

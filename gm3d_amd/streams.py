@@ -15,11 +15,14 @@ stream), and switches (`fused.ASYNC_WGRAD`, `NOGRAD_SPLIT`, `GM3D_PARALLEL_DECOD
                              An open one is joined to the origin by the audit itself (so that ending the capture is safe)
                              and then reported as RuntimeError naming who forked it.
 
-Outside a capture fork / join are plain wait_stream calls."""
+Outside a capture fork / join are plain wait_stream calls.
+SideStage, PinnedFeed, LookAhead: what feeds the captured steps between replays (a producer graph on a second stream one batch
+ahead, host draws through pinned memory, the loader one item ahead)."""
 import contextlib
 import sys
 
 import torch
+import torch.distributed as dist
 
 _ledgers = []          # stack of active audits (captures do not nest in the product; the stack keeps the code honest if they do)
 
@@ -75,7 +78,10 @@ def before_capture(fn):
 @contextlib.contextmanager
 def capture(graph, **kw):
     """torch.cuda.graph(graph, **kw) whose end is audited: RuntimeError (after a rescue join, so that the capture itself ends
-    cleanly) when a stream forked inside the body never came back to the capture-origin stream."""
+    cleanly) when a stream forked inside the body never came back to the capture-origin stream.
+    capture_error_mode, when the caller passes none: with a process group alive its watchdog thread polls events; only the capturing
+    thread's calls may abort a capture ("thread_local").  Without one, torch's default ("global")."""
+    kw.setdefault("capture_error_mode", "thread_local" if dist.is_initialized() else "global")
     if torch.cuda.is_available():
         dev = torch.device("cuda", torch.cuda.current_device())
         for fn in _before_capture:
@@ -107,3 +113,84 @@ def warm_up(fn, iters, device=None):
         for _ in range(iters):
             fn()
     torch.cuda.current_stream().wait_stream(side)
+
+
+class SideStage:
+    """A producer (one workgroup per cloud, most CUs idle: the fine-tune step's point sampling, Point-M2AE's grouping) captured as its
+    own graph and replayed on a second stream for the NEXT batch while the caller's training graph of the current batch runs.  A call:
+    take(batch, static_in); the caller's copy of the producer's outputs into the training graph's inputs; enqueue(next, static_in)
+    BEFORE the training graph is replayed, so that the two run side by side.  With no next batch the producer of a batch runs right
+    before its training: same results."""
+
+    def __init__(self, device=None):
+        self.stream = torch.cuda.Stream(device=device)
+        self.ready, self.staged, self.graph = torch.cuda.Event(), False, None
+
+    def capture(self, fn, generator=None):
+        """fn() captured on the stage's stream as the producer graph -> fn's result.  generator: registered with this graph only."""
+        self.graph = torch.cuda.CUDAGraph()
+        if generator is not None:
+            self.graph.register_generator_state(generator)
+        with capture(self.graph, stream=self.stream):
+            return fn()
+
+    def enqueue(self, src, static_in, before_replay=None):
+        """On the stage's stream, after everything the current stream has queued so far (the producer of `src`, and the copy that
+        consumed the previous staged results): src -> static_in, before_replay() (host work that belongs between the input copy and
+        the replay, on this stream), the producer graph, `ready`."""
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_event(ev)             # before the copy: src's producer runs on the caller's stream
+            static_in.copy_(src, non_blocking=True)
+            src.record_stream(self.stream)         # src was allocated on the caller's stream: its block must outlive this copy
+            if before_replay is not None:
+                before_replay()
+            self.graph.replay()
+            self.ready.record(self.stream)
+        self.staged = True
+
+    def take(self, src, static_in, before_replay=None):
+        """The current stream waits for `src`'s staged results: produced now if nothing is staged (first call, or no look-ahead given)."""
+        if not self.staged:
+            self.enqueue(src, static_in, before_replay)
+        torch.cuda.current_stream().wait_event(self.ready)
+        self.staged = False
+
+
+class PinnedFeed:
+    """Host arrays -> the given device tensors through two alternating pinned images of them, so that the copies are asynchronous (a
+    pageable copy would make the host wait for everything queued before it, once per step)."""
+
+    def __init__(self, *tensors):
+        self.tensors = tensors
+        self._pin = [[torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in tensors] for _ in range(2)]
+        self._ev, self._i = [torch.cuda.Event(), torch.cuda.Event()], 0
+
+    def push(self, arrays):
+        """numpy arrays, one per tensor -> the device tensors, on the current stream."""
+        i, self._i = self._i, self._i ^ 1
+        self._ev[i].synchronize()                  # the copies that last read this image (two pushes ago); nothing before its first record
+        for pin, dev, arr in zip(self._pin[i], self.tensors, arrays):
+            pin.copy_(torch.from_numpy(arr))
+            dev.copy_(pin, non_blocking=True)
+        self._ev[i].record(torch.cuda.current_stream())
+
+
+class LookAhead:
+    """The loader's items, each through move(item) (to the device), one ahead: while item i is trained, `next` is item i + 1 (None at
+    the end)."""
+
+    def __init__(self, loader, move):
+        self.loader, self.move, self.next = loader, move, None
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        moved = (self.move(item) for item in self.loader)
+        cur = next(moved, None)
+        while cur is not None:
+            self.next = next(moved, None)
+            yield cur
+            cur = self.next

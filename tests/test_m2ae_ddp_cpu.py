@@ -64,9 +64,9 @@ def test_engine_refuses_unsupported_setups():
 
 
 def test_look_ahead_loader_yields_in_order_with_the_next_batch():
-    from gm3d_amd import engine_pretrain_m2ae as EM
+    from gm3d_amd import streams
     batches = [torch.full((2, 4, 3), float(i)) for i in range(3)]
-    la = EM._LookAhead(batches, torch.device("cpu"))
+    la = streams.LookAhead(batches, lambda b: b.to(torch.device("cpu"), non_blocking=True))
     assert len(la) == 3
     seen = []
     for b in la:

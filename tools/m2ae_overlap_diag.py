@@ -19,7 +19,7 @@ for i in range(5):
 torch.cuda.synchronize()
 ev = lambda: torch.cuda.Event(enable_timing=True)
 # 1. each graph alone
-for name, fn, stream in (("group graph alone", g.group_graph.replay, g.side), ("train graph alone", g.train_graph.replay, torch.cuda.current_stream())):
+for name, fn, stream in (("group graph alone", g.group_graph.replay, g.stage.stream), ("train graph alone", g.train_graph.replay, torch.cuda.current_stream())):
     with torch.cuda.stream(stream):
         a, b = ev(), ev()
         a.record()
@@ -32,11 +32,11 @@ for name, fn, stream in (("group graph alone", g.group_graph.replay, g.side), ("
 t0, t1, s0, s1 = ev(), ev(), ev(), ev()
 main = torch.cuda.current_stream()
 t0.record(main)
-with torch.cuda.stream(g.side):
-    g.side.wait_event(t0)
-    s0.record(g.side)
+with torch.cuda.stream(g.stage.stream):
+    g.stage.stream.wait_event(t0)
+    s0.record(g.stage.stream)
     g.group_graph.replay()
-    s1.record(g.side)
+    s1.record(g.stage.stream)
 g.train_graph.replay()
 t1.record(main)
 torch.cuda.synchronize()
@@ -56,7 +56,7 @@ print("calls with look-ahead   %.3f ms" % loop(lambda i: g(pool[i % 4], next_pts
 print("calls without           %.3f ms" % loop(lambda i: g(pool[i % 4])))
 print("training graph only     %.3f ms" % loop(lambda i: g.train_graph.replay()))
 def both(i):
-    with torch.cuda.stream(g.side):
+    with torch.cuda.stream(g.stage.stream):
         g.group_graph.replay()
     g.train_graph.replay()
 print("both graphs, no copies  %.3f ms" % loop(both))
