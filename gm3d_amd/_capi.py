@@ -109,6 +109,8 @@ SIGNATURES = {
     "gm3d_radius_mask_bits_m": [_vp, _vp, _i, _f, _i, _i, _vp, _vp],
     "gm3d_attention_masked_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "gm3d_attention_masked_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
+    "gm3d_attention_long_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
+    "gm3d_attention_long_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
     "gm3d_mask_select": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
     "gm3d_bn_finalize": [_vp, ctypes.c_double, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "gm3d_pn1_finalize": [_vp, ctypes.c_double, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],

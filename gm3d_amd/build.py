@@ -33,6 +33,7 @@ SOURCES = {
     "gemm_f32.hip": [],
     "gather.hip": [],
     "attention_masked.hip": [],
+    "attention_long.hip": [],
     "vote.hip": [],
     "cls_tail.hip": [],
     "svm.hip": ["-ffp-contract=off"],

@@ -26,7 +26,7 @@ from ._capi import lib
 from . import fused, gemm
 from .embed import _c32
 from .fused import PER_BLOCK, block_params, weight_cache  # noqa: F401
-from .ops import _DT, _launch, _ptr, _stream
+from .ops import _DT, _launch, _ptr, _stream, launch_masked_attention
 
 
 # ----------------------------------------------------------------------------- kernel wrappers
@@ -62,16 +62,16 @@ def _attn_fwd(qkv, bits, B, T, H, hd, scale, out):
     if bits is None and hd == 64 and T <= 128:
         return fused._attention_fwd(qkv, B, T, H, scale, out=out)
     lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
-    _launch("gm3d_attention_masked_fwd", {"B": B, "T": T, "H": H, "HD": hd, "dtype": str(qkv.dtype)}, lib.gm3d_attention_masked_fwd,
-            _ptr(qkv), _ptr(bits), _ptr(out), _ptr(lse), B, T, H, hd, float(scale), _DT[qkv.dtype], _stream())
+    launch_masked_attention(False, {"B": B, "T": T, "H": H, "HD": hd, "dtype": str(qkv.dtype)},
+                            _ptr(qkv), _ptr(bits), _ptr(out), _ptr(lse), B, T, H, hd, float(scale), _DT[qkv.dtype], _stream())
     return out, lse
 
 
 def _attn_bwd(qkv, a, da, lse, bits, B, T, H, hd, scale, dqkv):
     if bits is None and hd == 64 and T <= 128:
         return fused._attention_bwd(qkv, a, da, lse, B, T, H, scale, dqkv=dqkv)
-    _launch("gm3d_attention_masked_bwd", {"B": B, "T": T, "H": H, "HD": hd, "dtype": str(qkv.dtype)}, lib.gm3d_attention_masked_bwd,
-            _ptr(qkv), _ptr(bits), _ptr(a), _ptr(da), _ptr(lse), _ptr(dqkv), B, T, H, hd, float(scale), _DT[qkv.dtype], _stream())
+    launch_masked_attention(True, {"B": B, "T": T, "H": H, "HD": hd, "dtype": str(qkv.dtype)},
+                            _ptr(qkv), _ptr(bits), _ptr(a), _ptr(da), _ptr(lse), _ptr(dqkv), B, T, H, hd, float(scale), _DT[qkv.dtype], _stream())
     return dqkv
 
 
@@ -82,7 +82,7 @@ def supported(x, blocks):
     C = x.shape[-1]
     H = blocks[0].attn.num_heads
     return (x.is_cuda and x.dim() == 3 and C % 8 == 0 and 8 <= C <= 512 and C % H == 0 and C // H in (16, 32, 64)
-            and x.shape[1] <= 512 and x.dtype in (torch.float32, torch.bfloat16))
+            and x.shape[1] <= 2048 and x.dtype in (torch.float32, torch.bfloat16))
 
 
 class MaskedStackFn(torch.autograd.Function):

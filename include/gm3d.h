@@ -654,6 +654,20 @@ int gm3d_attention_masked_fwd(const void *qkv, const unsigned *mask, void *out, 
                               int dtype, gm3d_stream_t stream);
 int gm3d_attention_masked_bwd(const void *qkv, const unsigned *mask, const void *out, const void *dout, const float *lse, void *dqkv,
                               int B, int T, int H, int HD, float scale, int dtype, gm3d_stream_t stream);
+/* The same operator for 513 <= T <= 2048 (gm3d_amd/csrc/attention_long.hip): arguments, layouts, mask semantics and rounding points
+ * of gm3d_attention_masked_fwd/bwd -- qkv (B,T,3,H,HD), HD in {16,32,64}; mask (B,T,ceil(T/32)) symmetric bitset or NULL; out
+ * (B,T,H*HD); lse (B,H,T) f32, 0 for a query with no allowed key, whose output row and gradient rows are zero; dqkv shaped like
+ * qkv; B * H <= (2^31 - 1) / 4.  T <= 512 and T > 2048 are GM3D_EUNSUPPORTED (T <= 512 belongs to gm3d_attention_masked_*: one
+ * owner per range), as is any other HD; a dtype other than GM3D_F32 / GM3D_BF16 or a NULL tensor is GM3D_EINVAL; all of it is
+ * decided on the host before any launch, and B = 0 returns GM3D_OK after these checks.  GM3D_BF16: flash-style MFMA kernels that
+ * stream the head through LDS in chunks of 64 rows, two buffers (forward: K, V and 256 query rows, at most 72 KiB; backward: one
+ * launch, Q, K, V, dO, lse and delta = rowsum(dO * O) of a chunk, at most 73 KiB); every row of dQ, dK and dV is written once by
+ * its one owner -- no atomics, no zero-fill, equal bits on every run.  GM3D_F32: the same kernels on the exact-fp32 MFMA (parity
+ * mode; fp32 images, forward at most 65 KiB, backward at most 131 KiB). */
+int gm3d_attention_long_fwd(const void *qkv, const unsigned *mask, void *out, float *lse, int B, int T, int H, int HD, float scale,
+                            int dtype, gm3d_stream_t stream);
+int gm3d_attention_long_bwd(const void *qkv, const unsigned *mask, const void *out, const void *dout, const float *lse, void *dqkv,
+                            int B, int T, int H, int HD, float scale, int dtype, gm3d_stream_t stream);
 
 /* ---- Voting evaluation of the fine-tuned classifier (gm3d_amd/csrc/vote.hip) --------------------------------------------
  * Replaces the per-vote loop of validate_vote / test_vote (Point-MAE_SA3D/tools/runner_finetune.py:293-309 and :421-437):
