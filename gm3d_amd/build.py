@@ -24,6 +24,7 @@ SOURCES = {
     "attention.hip": [],
     "rowops.hip": [],
     "embed.hip": [],
+    "guided.hip": [],
     "optim.hip": [],
     "gemm.hip": [],
     "gemm_nt.hip": [],

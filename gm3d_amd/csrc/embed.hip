@@ -17,6 +17,7 @@
 //     partial column sums finished by gm3d_colsum_finish (deterministic, no atomics, and -- unlike PyTorch's
 //     multi-block reduce_kernel on this stack -- safe under hipGraph replay).
 #include "common.hpp"
+#include "guided.hpp"
 
 namespace gm3d {
 
@@ -1297,7 +1298,8 @@ extern "C" int gm3d_rank_loss(const float* pred, const float* target, int B, int
                               gm3d_stream_t stream) {
     using namespace gm3d;
     if (!pred || !target || !out || !dpred || B < 1 || M < 1) return GM3D_EINVAL;
-    if (M > 64) return GM3D_EUNSUPPORTED;
+    if (M > GUIDED_MAX) return GM3D_EUNSUPPORTED;
+    if (M > GUIDED_NARROW) return launch_rank_loss_wide(pred, M, target, B, M, out, dpred, stream);      // guided.hip: one workgroup per cloud
     hipLaunchKernelGGL(rank_loss_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pred, M, target, M, out, dpred);
     GM3D_CHECK_LAUNCH();
     return GM3D_OK;
@@ -1307,9 +1309,14 @@ extern "C" int gm3d_rank_loss_tail(const float* pred, int ldp, const float* targ
                                    float* loss, gm3d_stream_t stream) {
     using namespace gm3d;
     if (!pred || !target || !out || !dpred || !tot || !loss || B < 1 || M < 1 || ldp < M) return GM3D_EINVAL;
-    if (M > 64) return GM3D_EUNSUPPORTED;
-    hipLaunchKernelGGL(rank_loss_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pred, ldp, target, M, out, dpred);
-    GM3D_CHECK_LAUNCH();
+    if (M > GUIDED_MAX) return GM3D_EUNSUPPORTED;
+    if (M > GUIDED_NARROW) {
+        const int rc = launch_rank_loss_wide(pred, ldp, target, B, M, out, dpred, stream);
+        if (rc != GM3D_OK) return rc;
+    } else {
+        hipLaunchKernelGGL(rank_loss_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pred, ldp, target, M, out, dpred);
+        GM3D_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(rank_loss_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)out, B, tot, loss);
     GM3D_CHECK_LAUNCH();
     return GM3D_OK;
@@ -1405,9 +1412,12 @@ extern "C" int gm3d_mask_select_b(const float* loss_pred, const float* noise, in
     using namespace gm3d;
     if (!loss_pred || !noise || !mask || !vis_ids || !mask_ids || B < 0 || L < 1) return GM3D_EINVAL;
     if (len_keep < 0 || len_loss < 0 || len_keep + len_loss > L) return GM3D_EINVAL;
-    if (L > 64) return GM3D_EUNSUPPORTED;
+    if (L > GUIDED_MAX) return GM3D_EUNSUPPORTED;
     if (B == 0) return GM3D_OK;
     if (id_pitch != 0 && id_pitch < L) return GM3D_EINVAL;
+    if (L > GUIDED_NARROW)                                   // guided.hip: one workgroup per cloud
+        return launch_mask_select_wide(loss_pred, noise, B, L, len_keep, len_loss, mask, mask_bool, vis_ids, mask_ids,
+                                       id_pitch ? id_pitch : len_keep, id_pitch ? id_pitch : L - len_keep, stream);
     hipLaunchKernelGGL(mask_select_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, loss_pred, noise, L, len_keep, len_loss,
                        mask, vis_ids, mask_ids, id_pitch ? id_pitch : len_keep, id_pitch ? id_pitch : L - len_keep, mask_bool);
     GM3D_CHECK_LAUNCH();

@@ -437,7 +437,7 @@ def step_forward_backward(model, model_ema, samples, epoch, args, grad_sync=None
             all_ids = (_arange_ids(B, L, samples.device), _arange_ids(B, 0, samples.device))
             outs_ema = teacher(samples, mask=visible_mask, num_visible=L, group=group, need_pix_pred=False, ids=all_ids)
             ids = None
-            if samples.is_cuda and L <= 64:       # mask (f32 and bool) + visible / masked id lists in one launch
+            if samples.is_cuda and L <= 512:      # mask (f32 and bool) + visible / masked id lists in one launch
                 mask, vis_ids, mask_ids, bool_masked_pos = teacher.generate_mask_ids(
                     outs_ema["loss_pred"], mask_ratio=args.mask_ratio, guide=True, epoch=epoch, total_epoch=args.epochs, noise=mask_noise,
                     want_bool=True)

@@ -20,9 +20,9 @@ import contextlib
 import torch
 
 from ._capi import lib
-from . import gemm
+from . import attention_pad, gemm
 from . import streams as _streams
-from .ops import _launch, _ptr, _stream, _DT, launch_masked_attention
+from .ops import _launch, _ptr, _stream, _DT
 
 LNC = 384
 
@@ -195,9 +195,9 @@ def _attention_fwd(qkv, B, T, H, scale, out=None):
     lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
     if T > 128:      # more tokens than one workgroup's LDS images hold (cfgs/config_3.yaml: 256 groups): the flash-style kernel of
         #              the hierarchical encoder with no mask (same qkv / out / lse layouts; T > 512: its streaming form, T <= 2048)
-        launch_masked_attention(False, {"B": B, "T": T, "H": H, "HD": 64, "dtype": str(qkv.dtype)},
-                                _ptr(qkv), None, _ptr(out), _ptr(lse), B, T, H, 64, float(scale), _DT[qkv.dtype], _stream())
-        return out, lse
+        #              bf16 between what its LDS holds and 513 tokens: the streaming form at 513 rows, the padding blocked as keys; the
+        #              lse that comes back is then (B,H,513) and goes to _attention_bwd as it is (attention_pad.py)
+        return attention_pad.forward(qkv, out, lse, B, T, H, scale)
     _launch("gm3d_attention_fwd", {"B": B, "T": T, "H": H, "dtype": str(qkv.dtype)}, lib.gm3d_attention_fwd, _ptr(qkv),
             _ptr(out), _ptr(lse), B, T, H, float(scale), _DT[qkv.dtype], _stream())
     return out, lse
@@ -226,9 +226,9 @@ def _attention_bwd(qkv, out, dout, lse, B, T, H, scale, dqkv=None):
     if dqkv is None:
         dqkv = torch.empty_like(qkv)
     if T > 128:
-        launch_masked_attention(True, {"B": B, "T": T, "H": H, "HD": 64, "dtype": str(qkv.dtype)},
-                                _ptr(qkv), None, _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), B, T, H, 64, float(scale), _DT[qkv.dtype], _stream())
-        return dqkv
+        # the flash-style kernel, its streaming form from 513 tokens, or (bf16, 257..512 tokens) the streaming form on padded operands
+        # (attention_pad.py)
+        return attention_pad.backward(qkv, out, dout, lse, dqkv, B, T, H, scale)
     _launch("gm3d_attention_bwd", {"B": B, "T": T, "H": H, "dtype": str(qkv.dtype)}, lib.gm3d_attention_bwd, _ptr(qkv),
             _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), B, T, H, float(scale), _DT[qkv.dtype], _stream())
     return dqkv

@@ -683,7 +683,7 @@ class _RankLossTail(torch.autograd.Function):
 
 def rank_loss_tail(pred_full, M, target):
     """rank_loss(pred_full[:, -M:], target) with the slice folded in; pred_full (B,L) f32, unit inner stride."""
-    if pred_full.dtype == torch.float32 and pred_full.dim() == 2 and pred_full.stride(1) == 1 and 1 <= M <= min(64, pred_full.shape[1]):
+    if pred_full.dtype == torch.float32 and pred_full.dim() == 2 and pred_full.stride(1) == 1 and 1 <= M <= min(512, pred_full.shape[1]):
         return _RankLossTail.apply(pred_full, M, target)
     return _RankLoss.apply(pred_full[:, -M:], target)
 

@@ -16,6 +16,7 @@ execution, not of results:
     the mini-PointNet's concat([global,local]) @ W is evaluated as local @ W_l + global @ W_g.
     Each of these is an exact algebraic identity (fp32 rounding-order differences only).
 """
+import ctypes
 from functools import partial
 
 import os
@@ -134,6 +135,7 @@ def _decoder_stream(device):
 FUSED_STACK = True   # False: per-op PyTorch modules below (kept as the in-package cross-check of the fused path)
 FUSED_EMBED = True   # same switch for the mini-PointNet token embed (gm3d_amd/embed.py)
 FUSED_HEADS = True   # ... and for pos_embed, the two heads, the mask-token expand and the ranking loss (gm3d_amd/heads.py)
+MAX_NUM_GROUP = 512  # tokens per cloud the guided-mask and ranking-loss kernels take (csrc/guided.hip); above: the aten formulations
 
 
 class DropPath(nn.Module):
@@ -330,7 +332,8 @@ def take(x, ids):
 @torch.no_grad()
 def generate_mask_ids(loss_pred, mask_ratio=0.75, guide=True, epoch=0, total_epoch=200, noise=None, want_bool=False):
     """Teacher-guided mask (P/:744-784) plus the id lists split_ids would derive from it, as ONE launch (gm3d_mask_select):
-    -> (mask (B,L) f32 0 keep / 1 remove, vis_ids (B,len_keep) int64, mask_ids (B,L-len_keep) int64[, the mask as bool]).  L <= 64."""
+    -> (mask (B,L) f32 0 keep / 1 remove, vis_ids (B,len_keep) int64, mask_ids (B,L-len_keep) int64[, the mask as bool]).  L <= 512
+    (one wavefront per cloud up to 64 tokens, one workgroup per cloud above: csrc/guided.hip)."""
     from ._capi import lib
     N, L = loss_pred.shape
     len_keep = int(L * (1 - mask_ratio))
@@ -345,8 +348,10 @@ def generate_mask_ids(loss_pred, mask_ratio=0.75, guide=True, epoch=0, total_epo
     order = torch.empty(N, L, dtype=torch.int64, device=dev)        # [visible ids | masked ids] per sample
     vis_ids, mask_ids = order[:, :len_keep], order[:, len_keep:]
     mask_b = torch.empty(N, L, dtype=torch.bool, device=dev) if want_bool else None
+    # the two id lists as the halves of `order` (pitch L); addressed through `order`: an empty half (mask_ratio 0) has no pointer of its own
     ops._launch("gm3d_mask_select", {"B": N, "L": L}, lib.gm3d_mask_select_b, ops._ptr(lp), ops._ptr(noise), N, L, len_keep,
-                len_loss, ops._ptr(mask), ops._ptr(mask_b), ops._ptr(vis_ids), ops._ptr(mask_ids), L, ops._stream())
+                len_loss, ops._ptr(mask), ops._ptr(mask_b), ctypes.c_void_p(order.data_ptr()),
+                ctypes.c_void_p(order.data_ptr() + 8 * len_keep), L, ops._stream())
     if want_bool:
         return mask, vis_ids, mask_ids, mask_b
     return mask, vis_ids, mask_ids
@@ -355,13 +360,16 @@ def generate_mask_ids(loss_pred, mask_ratio=0.75, guide=True, epoch=0, total_epo
 class MaskedAutoencoderViT(nn.Module):
     """GM3D Point-MAE (P/:30-188 live part).  The image-MAE constructor arguments are accepted and
     ignored, exactly as the reference ignores them for the point-cloud path (hyper-parameters are the
-    literals of P/:110-117)."""
+    literals of P/:110-117), except `num_group` (1..512, the reference's literal 64 by default): the number of FPS centres, i.e. of
+    tokens per cloud."""
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=1024, depth=24, num_heads=16,
                  decoder_embed_dim=512, decoder_depth=8, decoder_num_heads=16, mlp_ratio=4.0,
                  norm_layer=nn.LayerNorm, norm_pix_loss=False, asymmetric_decoder=False, mask_ratio=0.75,
-                 vis_mask_ratio=0.0, saliency=False):
+                 vis_mask_ratio=0.0, saliency=False, num_group=64):
         super().__init__()
+        if isinstance(num_group, bool) or int(num_group) != num_group or not 1 <= num_group <= MAX_NUM_GROUP:
+            raise ValueError("num_group must be an integer in 1..%d, got %r" % (MAX_NUM_GROUP, num_group))
         self.norm_pix_loss = norm_pix_loss
         self.vis_mask_ratio = vis_mask_ratio
         self.encoder_dims = 384
@@ -372,7 +380,8 @@ class MaskedAutoencoderViT(nn.Module):
         self.group_size = 32
         self.decoder_depth = 4
         self.decoder_num_heads = 6
-        self.num_group = 64
+        self.num_group = int(num_group)      # the reference's literal is 64 (P/:117); group_size stays 32: the fused patch loss and
+                                             # the reconstruction head are built for 32-point patches
 
         self.encoder = Encoder(encoder_channel=self.encoder_dims)
         self.pos_embed = nn.Sequential(nn.Linear(3, 128), nn.GELU(), nn.Linear(128, 384))
@@ -430,12 +439,12 @@ class MaskedAutoencoderViT(nn.Module):
 
     def forward(self, pts, mask, noaug=False, num_visible=None, group=None, need_pix_pred=True, tokens=None,
                 pos_all=None, ids=None, cut=False, tokens_visible=False):
-        """pts (B,N,3) f32, mask (B,64) bool (True = masked).  Extra keyword-only conveniences for the
+        """pts (B,N,3) f32, mask (B,num_group) bool (True = masked).  Extra keyword-only conveniences for the
         engine: `num_visible` (static visible count, avoids a host sync), `group` (a previously
         computed (neighborhood, center, neighborhood_org), e.g. the teacher's -- the student sees the
         identical samples), `need_pix_pred=False` (skip the reconstruction decoder whose output the
         teacher pass never reads, P/engine_pretrain.py:86-94), `tokens` / `pos_all` (this model's token embed and
-        positional embed of all 64 groups when the engine has already evaluated them -- neither depends on the mask;
+        positional embed of all num_group groups when the engine has already evaluated them -- neither depends on the mask;
         tokens_visible=True: `tokens` is (B,V,C), already restricted to the visible groups in vis_ids order)."""
         neighborhood, center, neighborhood_org = group if group is not None else self.group_divider(pts)
         vis_ids, mask_ids = ids if ids is not None else split_ids(mask, num_visible)   # ids: precomputed (generate_mask_ids)
@@ -532,7 +541,7 @@ class MaskedAutoencoderViT(nn.Module):
         }
 
     def forward_loss(self, pred, target, mask, mask_ids=None, full_pred=None):
-        """pred (B,M,96) = pix_pred[:, -M:], target = neighborhood (B,64,32,3), mask (B,64) bool (P/:384-412).
+        """pred (B,M,96) = pix_pred[:, -M:], target = neighborhood (B,G,32,3), mask (B,G) bool (P/:384-412).
         full_pred: the whole pix_pred (B,L,96) `pred` was sliced from (optional): the fused loss then takes the slice itself and its
         backward returns the whole tensor's gradient (no separate zero-fill + copy for the slice)."""
         N, t, n, D = target.shape
@@ -572,7 +581,7 @@ class MaskedAutoencoderViT(nn.Module):
             noise = torch.rand(N, L, device=loss_pred.device)
         else:
             noise = noise.to(loss_pred.device, torch.float32).clone()
-        if loss_pred.is_cuda and L <= 64:
+        if loss_pred.is_cuda and L <= MAX_NUM_GROUP:
             return self.generate_mask_ids(loss_pred, mask_ratio, guide, epoch, total_epoch, noise)[0]
         if len_loss > 0:
             forced = torch.argsort(loss_pred.float(), dim=1)[:, L - len_loss:]
@@ -592,7 +601,7 @@ class MaskedAutoencoderViT(nn.Module):
         full_pred[:, -M:] was sliced from (optional; the fused loss then folds the slice and its backward in)."""
         loss_pred = loss_pred.float()
         loss_target = loss_target.float()
-        if relative and FUSED_HEADS and loss_pred.is_cuda and loss_pred.shape[1] <= 64:
+        if relative and FUSED_HEADS and loss_pred.is_cuda and loss_pred.shape[1] <= MAX_NUM_GROUP:
             from . import heads
             if full_pred is not None and full_pred.dtype == torch.float32:
                 return heads.rank_loss_tail(full_pred, loss_pred.shape[1], loss_target)

@@ -113,7 +113,7 @@ def reconstruct_geomask(model, teacher, pts, epoch, total_epoch, mask_ratio, mas
             group = teacher.group_divider(pts)
             all_ids = (_arange_ids(B, L, dev), _arange_ids(B, 0, dev))
             outs_ema = teacher(pts, mask=_all_false(B, L, dev), num_visible=L, group=group, need_pix_pred=False, ids=all_ids)
-            if pts.is_cuda and L <= 64:
+            if pts.is_cuda and L <= 512:
                 _, vis_ids, mask_ids, mask = teacher.generate_mask_ids(outs_ema["loss_pred"], mask_ratio=mask_ratio, guide=True,
                                                                        epoch=epoch, total_epoch=total_epoch, noise=mask_noise,
                                                                        want_bool=True)

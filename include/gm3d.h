@@ -328,7 +328,8 @@ int gm3d_lin3_gelu_bwd(const void *dout, const float *x, const float *w, const f
 int gm3d_lin3_finish(const double *partial, int nrows, int C, float *dW, float *db, gm3d_stream_t stream);
 
 /* Pairwise ranking loss of forward_learning_loss(relative=True) (models_mae_learn_loss.py:795-805), per sample:
- * out (B,2) f32 = [sum of pair terms, number of ordered pairs]; dpred (B,M) = d(sum of pair terms)/d pred.  M <= 64. */
+ * out (B,2) f32 = [sum of pair terms, number of ordered pairs]; dpred (B,M) = d(sum of pair terms)/d pred.
+ * M <= 64: one wavefront per sample; 65..512: one workgroup per sample (guided.hip); above: GM3D_EUNSUPPORTED. */
 int gm3d_rank_loss(const float *pred, const float *target, int B, int M, float *out, float *dpred,
                    gm3d_stream_t stream);
 /* The whole loss_learn of engine_pretrain.py:156-171 on the last M columns of a (B, ldp)-pitched prediction (pred points at the first
@@ -386,7 +387,9 @@ int gm3d_pn1_bwd_finalize(const double *q, const double *mcov, const float *w, c
 /* Teacher-guided mask (models_mae_learn_loss.py:744-784 generate_mask) and the visible / masked token id lists the
  * boolean-mask indexing of :298-299,649-650 produces, in one launch.  loss_pred, noise (B,L) f32; the len_loss tokens of
  * highest loss_pred are always masked, the others are ranked by noise ((value, index) order) and the first len_keep stay
- * visible.  mask (B,L) f32: 0 keep / 1 remove; vis_ids (B,len_keep), mask_ids (B,L-len_keep) int64 ascending.  L <= 64.
+ * visible.  mask (B,L) f32: 0 keep / 1 remove; vis_ids (B,len_keep), mask_ids (B,L-len_keep) int64 ascending.
+ * L <= 64: one wavefront per sample; 65..512: one workgroup per sample, keys compared as order-preserving integers (guided.hip): exactly
+ * len_keep tokens are visible and every id is written once whatever the inputs hold; above: GM3D_EUNSUPPORTED.
  * id_pitch = 0: the two id arrays are dense; id_pitch >= L: their row pitch in elements (vis_ids = order, mask_ids = order + len_keep
  * of one (B,id_pitch) buffer gives the [visible | masked] permutation gm3d_token_assemble_* consume). */
 int gm3d_mask_select(const float *loss_pred, const float *noise, int B, int L, int len_keep, int len_loss, float *mask,
