@@ -105,9 +105,9 @@ class EmbedFn(torch.autograd.Function):
                 _ptr(bf), _ptr(a1), R, C1, dt_id, _stream())
         # ---- conv2 + max-pool ----
         W2 = weight_cache.get(w2, adt).reshape(C2, C1)
-        pool_fused = gemm.FUSE_POOL and ((K == 32 and gemm.supported(a1, W2)) or (K == 16 and gemm.pool16_supported(a1, W2)))
-        if pool_fused:      # conv2 + bias + max-pool in one launch: f is written for conv3, (fg, arg1) come from the same tile
-            f, fg, arg1 = gemm.linear_pool(a1, W2, _c32(b2), bias_after_pool=False, want_rows=True, group_rows=K)
+        pool = gemm.route_pool(a1, W2, K)
+        if pool[0] != "split":      # conv2 + bias + max-pool in one launch: f is written for conv3, (fg, arg1) come from the same tile
+            f, fg, arg1 = gemm.linear_pool(a1, W2, _c32(b2), bias_after_pool=False, want_rows=True, group_rows=K, route=pool)
         else:
             f = linear_bias(a1, W2, b2, adt)
             fg = torch.empty(BG, C2, dtype=adt, device=dev)
@@ -122,12 +122,10 @@ class EmbedFn(torch.autograd.Function):
         # the product with the BatchNorm behind it in its epilogue (csrc/gemm_ws.hip EPI 4 / 5): train mode -> its statistics come
         # out of the product's launch (no second pass over the (rows, 512) tensor); eval mode (the EMA teacher) -> BN + ReLU applied
         # there, the product itself never reaches HBM
-        fuse_bn = K in (16, 32) and gemm.ws_bn_supported(f, W3l, t, group_rows=K)
+        bn = gemm.route_bn(f, W3l, t, K, training, vis is not None)[0]
         y0 = st = None
         if training:
-            # (groups of 16 rows: the statistics epilogue measured SLOWER than product + pass -- 711 vs 355 + 245 us at 1,048,576 rows,
-            #  tools/m2ae_gemm_shapes.py -- so only the eval-mode apply epilogue is used there: 654 vs 355 + 388)
-            if fuse_bn and (K == 32 or gemm.WS_BN_STATS16):
+            if bn == "stats":
                 y0, part = gemm.linear_ws_bn_stats(f, W3l, t, group_rows=K)
                 st = _finish(part, part.shape[0], 2 * C3)
             else:
@@ -154,7 +152,7 @@ class EmbedFn(torch.autograd.Function):
             inv = torch.empty(BG, dtype=torch.int32, device=dev)
             _launch("gm3d_group_select_maps", {"B": B, "V": Gs, "G": G}, lib.gm3d_group_select_maps, _ptr(vis), vis.stride(0), B,
                     Gs, G, _ptr(sel), _ptr(inv), _stream())
-        if not training and fuse_bn and vis is None:
+        if bn == "apply":
             a2 = gemm.linear_ws_bn_apply(f, W3l, t, scale2, shift2, group_rows=K)
         else:
             if y0 is None:
@@ -165,9 +163,10 @@ class EmbedFn(torch.autograd.Function):
         # ---- conv4 + max-pool ----
         W4 = weight_cache.get(w4, adt).reshape(C4, C3)
         b4f = _c32(b4)
-        if gemm.FUSE_POOL and ((K == 32 and gemm.supported(a2, W4)) or (K == 16 and gemm.pool16_supported(a2, W4))):
+        pool = gemm.route_pool(a2, W4, K)
+        if pool[0] != "split":
             # conv4 + max-pool + bias: the (rows, 384) product never reaches HBM (the backward needs only arg2)
-            _, tok, arg2 = gemm.linear_pool(a2, W4, b4f, bias_after_pool=True, want_rows=False, group_rows=K)
+            _, tok, arg2 = gemm.linear_pool(a2, W4, b4f, bias_after_pool=True, want_rows=False, group_rows=K, route=pool)
         else:
             z = gemm.mm(a2, W4)     # groups of k != 32 points (Point-M2AE level 0: k = 16)
             tok = torch.empty(BGs, C4, dtype=adt, device=dev)

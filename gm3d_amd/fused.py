@@ -22,6 +22,7 @@ import torch
 from ._capi import lib
 from . import attention_pad, gemm
 from . import streams as _streams
+from .gemm import bias_gelu_bwd, bias_gelu_fwd  # noqa: F401  (their home is beside the products they follow)
 from .ops import _launch, _ptr, _stream, _DT
 
 LNC = 384
@@ -151,34 +152,6 @@ def residual_ln_bwd(dh, gin, x, mean, rstd, gamma, rowscale, rows_per_sample, ac
     _launch("gm3d_colsum_finish", {"rows": nrows, "cols": 3 * LNC}, lib.gm3d_colsum_finish, _ptr(partial), nrows, 3 * LNC,
             3 * LNC, _ptr(sums), 0, _stream())
     return dx, dy, sums
-
-
-def bias_gelu_fwd(f, bias, adt, g=None):
-    R, C = f.shape
-    if g is None:
-        g = torch.empty_like(f)
-    _launch("gm3d_bias_gelu_fwd", {"R": R, "C": C, "dtype": str(adt)}, lib.gm3d_bias_gelu_fwd, _ptr(f), _ptr(bias), _ptr(g),
-            R, C, _DT[adt], _stream())
-    return g
-
-
-def bias_gelu_bwd(dg, f, bias, adt, df=None, partial=None):
-    """-> df (R,C) adt, dbias (C) f32 (None when `partial`, a slice of a batched buffer, is given)."""
-    R, C = f.shape
-    if df is None:
-        df = torch.empty_like(f)
-    nrows = lib.gm3d_gelu_partial_rows(R)
-    defer = partial is not None
-    if partial is None:
-        partial = torch.empty(nrows, C, dtype=torch.float32, device=f.device)
-    _launch("gm3d_bias_gelu_bwd", {"R": R, "C": C, "dtype": str(adt)}, lib.gm3d_bias_gelu_bwd, _ptr(dg), _ptr(f), _ptr(bias),
-            _ptr(df), _ptr(partial), R, C, _DT[adt], _stream())
-    if defer:
-        return df, None
-    db = torch.empty(C, dtype=torch.float32, device=f.device)
-    _launch("gm3d_colsum_finish", {"rows": nrows, "cols": C}, lib.gm3d_colsum_finish, _ptr(partial), nrows, C, C, _ptr(db), 0,
-            _stream())
-    return df, db
 
 
 def finish_batched(partial, out):
@@ -385,7 +358,7 @@ class TransformerStackFn(torch.autograd.Function):
         # LayerNorm folded into the GEMMs around it (bf16 path): proj / fc2 write the fp32 residual stream + per-tile row
         # statistics in their epilogue (gm3d_gemm_tn_bf16_res), qkv / fc1 normalise while they stage their A operand
         # (gm3d_gemm_tn_bf16_lna).  Stand-alone LayerNorm passes remain only in front of the first block and behind the last.
-        fuse_ln = (gemm.ENABLED and gemm.FUSE_LN and gemm.FUSE_GELU and adt == torch.bfloat16 and x.is_cuda
+        fuse_ln = (gemm.fuse_ln() and adt == torch.bfloat16 and x.is_cuda
                    and all(gemm.supported(posa, weight_cache.get(params[i * PER_BLOCK + k], adt)) or k == 9
                            for i in range(nblk) for k in (2, 3, 7)))
         st1 = None
@@ -435,17 +408,13 @@ class TransformerStackFn(torch.autograd.Function):
             x1, h2, m2, r2 = residual_ln_fwd(u, p, bproj, dp1, T, None, ln2w, ln2b, eps, adt, R, h=H2[i] if need else None)
             yield
             W1 = weight_cache.get(w1, adt)
-            if gemm.FUSE_GELU and gemm.supported(h2, W1):
-                # fc1 + bias + GELU in the GEMM epilogue; the pre-activation is only written when a backward follows
-                fo = torch.empty(R, W1.shape[0], dtype=adt, device=dev) if need else None
-                if gemm.dma_supported(h2, W1):
-                    f, g = gemm.linear_gelu_dma(h2, W1, b1, f_out=fo, g_out=GG[i] if need else None, bm=gemm.dma_bm(R))
-                else:
-                    f, g = gemm.linear_gelu(h2, W1, b1, f_out=fo, g_out=GG[i] if need else None)
-            else:
+            if gemm.route_gelu(h2, W1)[0] == "split":      # two launches: run here, for the yield between them
                 f = gemm.mm(h2, W1)
                 yield
                 g = bias_gelu_fwd(f, b1, adt, g=GG[i] if need else None)
+            else:
+                # fc1 + bias + GELU in the GEMM epilogue; the pre-activation is only written when a backward follows
+                f, g = gemm.mm_gelu(h2, W1, b1, need, g_out=GG[i] if need else None)
             yield
             o = gemm.mm(g, weight_cache.get(w2, adt))
             yield
@@ -490,16 +459,14 @@ class TransformerStackFn(torch.autograd.Function):
         # it wants fc2.weight^T (and proj.weight^T for the attention branch), produced for the whole stack by one strided
         # transposing copy each from the optimizer's flat bf16 shadow
         w2s = [weight_cache.get(params[i * PER_BLOCK + 9], adt) for i in range(nblk)]
-        fuse_mlp_bwd = gemm.ENABLED and gemm.FUSE_GELU_BWD and adt == torch.bfloat16 and dh.is_cuda
+        gelu_bwd = gemm.route_gelu_bwd(dh, w2s[0])
+        fuse_mlp_bwd = gelu_bwd[0] != "split"
         if fuse_mlp_bwd:
             # fc2^T (nblk, 4C, C), proj^T (nblk, C, C) and -- fc1 / qkv input gradients as TN products on the LDS-DMA ring kernel (N = 384
             # columns, K = 1536 / 1152: its regime) -- fc1^T (nblk, C, 4C), qkv^T (nblk, C, 3C): ONE transposing launch for the four
             W2T, WPT, W1T, WQT = gemm.stacked_transposes(
                 [w2s] + [[weight_cache.get(params[i * PER_BLOCK + k], adt) for i in range(nblk)] for k in (3, 7, 2)])
-        dma_bwd = fuse_mlp_bwd and gemm.dma_supported(dh.reshape(R, C), W2T[0])
-        bm_bwd = gemm.dma_bm(R)
-        PGL = torch.empty(nblk, ((R + bm_bwd - 1) // bm_bwd if dma_bwd else gemm.tile_rows(R)) if fuse_mlp_bwd
-                          else lib.gm3d_gelu_partial_rows(R), 4 * C, dtype=torch.float32, device=dev)
+        PGL = torch.empty(nblk, gelu_bwd[2], 4 * C, dtype=torch.float32, device=dev)
         SGL = torch.empty(nblk, 4 * C, dtype=torch.float32, device=dev)
         dp2_last = meta["dp"][nblk - 1][1]
         G, d_o, _ = residual_ln_bwd(dh, None, xf, mf, rf, final_w, dp2_last, T, None, True, adt, R, dy=DO[nblk - 1],
@@ -518,8 +485,7 @@ class TransformerStackFn(torch.autograd.Function):
             # mlp branch: x2 = x1 + dp2 * (g @ W2^T + b2)
             gi[10] = db2
             if fuse_mlp_bwd:
-                df = (gemm.linear_gelu_bwd_dma(d_o, W2T[i], f, b1, DF[i], PGL[i], bm=bm_bwd) if dma_bwd
-                      else gemm.linear_gelu_bwd(d_o, W2T[i], f, b1, DF[i], PGL[i]))
+                df = gemm.mm_gelu_bwd(d_o, W2T[i], f, b1, DF[i], PGL[i], gelu_bwd)
             else:
                 dg = gemm.mm_nn(d_o, weight_cache.get(w2, adt))
                 df, _ = bias_gelu_bwd(dg, f, b1, adt, df=DF[i], partial=PGL[i])

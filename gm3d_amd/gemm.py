@@ -8,15 +8,21 @@ bf16 operands in the kernels' layout (`_rows_ok`) run on the hand-written MFMA k
 widths), gemm_ring.hip (LDS-DMA ring), gemm_dma.hip (LDS-DMA double buffer, bm x bn tiles), gemm_ws.hip (weight-stationary, tall
 products), gemm_nt.hip (weight gradients); `choose` is the per-shape table (tools/gemm_kbench.py -> profiles/r03_gemm_kbench.txt).
 fp32 operands run on csrc/gemm_f32.hip under F32_OWN and on the BLAS library otherwise; the library is also where bf16 operands
-outside the layout rules end (never on the bf16 step's path: tools/leftover_sites.py lists none).  The fused-epilogue forms (fc1 +
-GELU, fc2-dgrad + GELU', conv + max-pool, LayerNorm / BatchNorm epilogues) are entry points of their own below; their callers
-pick them by the same predicates.  DESIGN.md 3b' has the design and the measurements."""
+outside the layout rules end (never on the bf16 step's path: tools/leftover_sites.py lists none).
+
+The products with a fused epilogue are decided here too, by pure functions like `route`: fc1 + GELU (`route_gelu` under `mm_gelu`),
+fc2-dgrad + GELU' (`route_gelu_bwd` under `mm_gelu_bwd`), conv + max-pool (`route_pool` under `linear_pool`), conv3 + BatchNorm
+(`route_bn`, for linear_ws_bn_stats / _apply); "split" / "none" is the plain product and a row pass behind it.  The two block stacks
+differ in ONE argument, `tiled`: where the 192-column LDS-DMA kernel does not take fc1, TransformerStackFn falls back to the tiled
+gm3d_gemm_tn_bf16_gelu (its first fused form, older than csrc/gemm_dma.hip), MaskedStackFn to the split form (it got the epilogues
+later, for the 192 / 384-wide stacks, on the LDS-DMA kernel alone: a 128-wide stack takes whole tiles and still runs split).  The
+LayerNorm epilogues (FUSE_LN, off) stay entry points their one caller picks.  DESIGN.md 3b' has the design and the measurements."""
 import ctypes
 
 import torch
 
 from ._capi import lib
-from .ops import _launch, _ptr, _stream
+from .ops import _DT, _launch, _ptr, _stream
 
 
 ENABLED = True            # module attributes below: flipped by the equality tests and tools/, not environment switches
@@ -186,6 +192,10 @@ def linear_gelu_dma(x, w, bias, f_out=None, g_out=None, bm=64):
 FUSE_LN = False
 
 
+def fuse_ln():
+    return ENABLED and FUSE_LN and FUSE_GELU      # (the LayerNorm forms' fc1 is the fused fc1 + GELU)
+
+
 def linear_res(x, w, bias, res, rowscale, rows_per_sample, add, bm=None):
     """proj / fc2 with the residual epilogue: -> (U (M,384) f32 = res + rowscale * (bf16(x @ w^T) + bias) + add, its bf16 copy,
     stats (3,M,2) f32 = per 128-column tile (mean, sum of squared deviations))."""
@@ -231,6 +241,35 @@ def linear_gelu(x, w, bias, f_out=None, g_out=None):
     return _tn("gm3d_gemm_tn_bf16_gelu", x, w, bias, (f_out, g_out))
 
 
+def bias_gelu_fwd(f, bias, adt, g=None):
+    R, C = f.shape
+    if g is None:
+        g = torch.empty_like(f)
+    _launch("gm3d_bias_gelu_fwd", {"R": R, "C": C, "dtype": str(adt)}, lib.gm3d_bias_gelu_fwd, _ptr(f), _ptr(bias), _ptr(g),
+            R, C, _DT[adt], _stream())
+    return g
+
+
+def route_gelu(x, w, tiled=True, fuse=True):
+    """What runs fc1 + bias + GELU over x (M,K), w (N,K) -> (kind, launch arguments): "dma" with bm (csrc/gemm_dma.hip: N % 192 == 0),
+    "own" (csrc/gemm.hip, 128-column tiles) or "split" (`mm`, then gm3d_bias_gelu_fwd).  tiled: may "own" be answered -- the one
+    difference between the two stacks (module docstring); fuse: the caller's own switch (masked_stack.FUSE_GELU).  Pure, like `route`."""
+    if fuse and FUSE_GELU and dma_supported(x, w):
+        return "dma", {"bm": dma_bm(x.shape[0])}
+    return ("own", {}) if fuse and tiled and FUSE_GELU and supported(x, w) else ("split", {})
+
+
+def mm_gelu(x, w, bias, want_f, g_out=None, tiled=True, fuse=True):
+    """-> (f, g = GELU(x @ w^T + bias)) on what `route_gelu` names; f, the pre-activation WITHOUT bias (what the backward re-reads), is
+    written when want_f (the split form always has it)."""
+    kind, args = route_gelu(x, w, tiled, fuse)
+    if kind == "split":
+        f = mm(x, w)
+        return f, bias_gelu_fwd(f, bias, x.dtype, g=g_out)
+    f = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device) if want_f else None
+    return _tn("gm3d_gemm_tn_bf16_dma_gelu" if kind == "dma" else "gm3d_gemm_tn_bf16_gelu", x, w, bias, (f, g_out), *args.values())
+
+
 USE_WS = True             # tall products (M >= 32768) of the mini-PointNet shapes on the weight-stationary kernel (csrc/gemm_ws.hip):
 #                           40 / 104 / 55 / 104 / 43 us against 53 / 142 / 76 / 112 / 47 on the tiled kernels (r03 table), -0.13 ms per step
 USE_WS_POOL = True        # ... and conv + max-pool (the product computed non-transposed for these tiles: lane = column, so the pool is a
@@ -262,12 +301,24 @@ def linear_tn_ws(x, w, bias=None, out=None):
 WS_BN = True             # second_conv.0 with the BatchNorm behind it in the product's epilogue (eval: apply + ReLU; train: the statistics)
 
 
-WS_BN_STATS16 = False    # the train-mode statistics epilogue for 16-row groups: slower than the separate pass (see embed.py); kept as a tested entry point
+WS_BN_STATS16 = False    # the train-mode statistics epilogue for 16-row groups: slower than the separate pass (route_bn); kept as a tested entry point
 
 
 def ws_bn_supported(x, w, t, group_rows=32):
     return (WS_BN and group_rows in (16, 32) and ws_supported(x, w) and x.shape[0] % 32 == 0 and t.dtype == torch.bfloat16 and t.is_contiguous()
             and t.shape == (x.shape[0] // group_rows, w.shape[0]) and lib.gm3d_gemm_ws_stats_rows(x.shape[0], w.shape[0], x.shape[1]) > 0)
+
+
+def route_bn(x, w, t, group_rows, training, selected):
+    """Does conv3, x (M,K) @ w (N,K)^T + t[row // group_rows], carry the BatchNorm behind it in its epilogue -> (kind, launch arguments):
+    "stats" (train: linear_ws_bn_stats), "apply" (eval: linear_ws_bn_apply; not when only `selected` groups go on) or "none".  Pure."""
+    if not ws_bn_supported(x, w, t, group_rows):
+        return "none", {}
+    if training:
+        # (groups of 16 rows: the statistics epilogue measured SLOWER than product + pass -- 711 vs 355 + 245 us at 1,048,576 rows,
+        #  tools/m2ae_gemm_shapes.py -- so only the eval-mode apply epilogue is used there: 654 vs 355 + 388)
+        return ("stats", {"group_rows": group_rows}) if group_rows == 32 or WS_BN_STATS16 else ("none", {})
+    return ("none", {}) if selected else ("apply", {"group_rows": group_rows})
 
 
 def linear_ws_bn_apply(x, w, t, scale, shift, slope=0.0, group_rows=32):
@@ -449,30 +500,37 @@ def pool16_supported(x, w):
             and x.shape[1] == w.shape[1] and bool(lib.gm3d_gemm_ws_supported(w.shape[0], w.shape[1], 1)))
 
 
-def linear_pool(x, w, bias, bias_after_pool, want_rows, group_rows=32):
-    """Conv1d(k=1) over (groups*group_rows, K) rows + max over each group's rows in the GEMM epilogue (group_rows 32; 16 on the
-    weight-stationary kernel only: pool16_supported).
+def route_pool(x, w, group_rows):
+    """What runs conv + max over each group's rows, x (groups * group_rows, K) @ w (N,K)^T -> (kind, launch arguments): "ws16" (groups
+    of 16, weight-stationary kernel only), "ws" (csrc/gemm_ws.hip), "dma" with bm / bn (csrc/gemm_dma.hip), "own" (csrc/gemm.hip) or
+    "split" (the product, then the caller's gm3d_group_max_fwd).  Pure, like `route`."""
+    N = w.shape[0]
+    if not FUSE_POOL or not (pool16_supported(x, w) if group_rows == 16 else group_rows == 32 and supported(x, w)):
+        return "split", {}
+    if group_rows == 16:
+        return "ws16", {"group_rows": 16}
+    if ws_supported(x, w, pool=True):
+        return "ws", {}
+    if POOL_ON_DMA and (N % 192 == 0 or N % 128 == 0):
+        return "dma", {"bm": 128, "bn": 192 if N % 192 == 0 else 128}
+    return "own", {}
+
+
+def linear_pool(x, w, bias, bias_after_pool, want_rows, group_rows=32, route=None):
+    """Conv1d(k=1) over (groups*group_rows, K) rows + max over each group's rows in the GEMM epilogue, on what `route_pool` names
+    (route: its answer, when the caller has asked already).
     -> (rows (M,N) bf16 | None, pooled (M/group_rows,N) bf16, argmax (M/group_rows,N) uint8)."""
+    kind, args = route or route_pool(x, w, group_rows)
+    if kind == "split":
+        raise ValueError("no kernel carries the pool epilogue for this product: run it split (route_pool)")
     M, K = x.shape
     N = w.shape[0]
     rows = torch.empty(M, N, dtype=torch.bfloat16, device=x.device) if want_rows else None
     pooled = torch.empty(M // group_rows, N, dtype=torch.bfloat16, device=x.device)
     arg = torch.empty(M // group_rows, N, dtype=torch.uint8, device=x.device)
-    if group_rows == 16:
-        _launch("gm3d_gemm_tn_bf16_ws_pool", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_ws_poolg, _ptr(x), _ptr(w), _ptr(bias), _ptr(rows),
-                _ptr(pooled), _ptr(arg), M, N, K, x.stride(0), w.stride(0), N, N, int(bias_after_pool), 16, _stream())
-        return rows, pooled, arg
-    if ws_supported(x, w, pool=True):
-        _launch("gm3d_gemm_tn_bf16_ws_pool", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_ws_pool, _ptr(x), _ptr(w), _ptr(bias), _ptr(rows),
-                _ptr(pooled), _ptr(arg), M, N, K, x.stride(0), w.stride(0), N, N, int(bias_after_pool), _stream())
-        return rows, pooled, arg
-    if POOL_ON_DMA and N % 8 == 0 and (N % 192 == 0 or N % 128 == 0):
-        bn = 192 if N % 192 == 0 else 128
-        _launch("gm3d_gemm_tn_bf16_dma_pool", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_dma_pool, _ptr(x), _ptr(w), _ptr(bias),
-                _ptr(rows), _ptr(pooled), _ptr(arg), M, N, K, x.stride(0), w.stride(0), N, N, int(bias_after_pool), 128, bn, _stream())
-        return rows, pooled, arg
-    _launch("gm3d_gemm_tn_bf16_pool", {"M": M, "N": N, "K": K}, lib.gm3d_gemm_tn_bf16_pool, _ptr(x), _ptr(w), _ptr(bias), _ptr(rows),
-            _ptr(pooled), _ptr(arg), M, N, K, x.stride(0), w.stride(0), N, N, int(bias_after_pool), _stream())
+    name = "gm3d_gemm_tn_bf16_" + {"ws16": "ws_pool", "ws": "ws_pool", "dma": "dma_pool", "own": "pool"}[kind]
+    _launch(name, {"M": M, "N": N, "K": K}, getattr(lib, name + "g" * (kind == "ws16")), _ptr(x), _ptr(w), _ptr(bias), _ptr(rows), _ptr(pooled), _ptr(arg), M, N, K,
+            x.stride(0), w.stride(0), N, N, int(bias_after_pool), *args.values(), _stream())
     return rows, pooled, arg
 
 
@@ -727,6 +785,46 @@ def linear_gelu_bwd_dma(d_o, w2t, f, bias, df, colpart, bm=64):
             _ptr(f), _ptr(bias), _ptr(df), _ptr(colpart), M, N, K, d_o.stride(0), w2t.stride(0), f.stride(0), df.stride(0), int(bm),
             _stream())
     return df
+
+
+def bias_gelu_bwd(dg, f, bias, adt, df=None, partial=None):
+    """-> df (R,C) adt, dbias (C) f32 (None when `partial`, a slice of a batched buffer, is given)."""
+    R, C = f.shape
+    if df is None:
+        df = torch.empty_like(f)
+    nrows = lib.gm3d_gelu_partial_rows(R)
+    defer = partial is not None
+    if partial is None:
+        partial = torch.empty(nrows, C, dtype=torch.float32, device=f.device)
+    _launch("gm3d_bias_gelu_bwd", {"R": R, "C": C, "dtype": str(adt)}, lib.gm3d_bias_gelu_bwd, _ptr(dg), _ptr(f), _ptr(bias),
+            _ptr(df), _ptr(partial), R, C, _DT[adt], _stream())
+    if defer:
+        return df, None
+    db = torch.empty(C, dtype=torch.float32, device=f.device)
+    _launch("gm3d_colsum_finish", {"rows": nrows, "cols": C}, lib.gm3d_colsum_finish, _ptr(partial), nrows, C, C, _ptr(db), 0,
+            _stream())
+    return df, db
+
+
+def route_gelu_bwd(d_o, w2, tiled=True, fuse=True):
+    """What runs df = (d_o @ fc2.weight) * GELU'(f + bias) with fc1's bias-gradient partials, d_o (M,C), w2 (C,N) = fc2.weight in the
+    activation type (the kernels read its transposed copy (N,C): fresh from stacked_transposes, so dense and aligned)
+    -> (kind, launch arguments, partial rows): `route_gelu`'s kinds and arguments, and how many rows of column-sum partials the
+    kernel of that kind writes -- the one place that knows.  Pure, like `route`."""
+    M, N = d_o.shape[0], w2.shape[1]
+    ok = (fuse and FUSE_GELU_BWD and ENABLED and _rows_ok(d_o, 64) and w2.is_cuda and w2.dtype == torch.bfloat16 and w2.dim() == 2
+          and w2.shape[0] == d_o.shape[1] and N % 128 == 0)
+    if ok and USE_DMA and N % 192 == 0:
+        bm = dma_bm(M)
+        return "dma", {"bm": bm}, -(-M // bm)
+    return ("own", {}, tile_rows(M)) if ok and tiled else ("split", {}, lib.gm3d_gelu_partial_rows(M))
+
+
+def mm_gelu_bwd(d_o, w2t, f, bias, df, colpart, route):
+    """df on what `route` (route_gelu_bwd's answer for this stack) names; w2t (N,C) = fc2.weight^T; colpart: `route`'s partial rows."""
+    if route[0] == "split":
+        return bias_gelu_bwd(mm(d_o, w2t), f, bias, d_o.dtype, df=df, partial=colpart)[0]
+    return (linear_gelu_bwd_dma if route[0] == "dma" else linear_gelu_bwd)(d_o, w2t, f, bias, df, colpart, **route[1])
 
 
 MULTI_TRANSPOSE = True    # the four transposed weight shadows of a stack's backward in ONE launch (gm3d_transpose_bf16_multi)

@@ -121,14 +121,8 @@ class MaskedStackFn(torch.autograd.Function):
             p = gemm.mm(a, weight_cache.get(wproj, adt))
             s2, h2, m2, r2 = _add_ln_fwd(s1, p, _c32(bproj), dp1, T, None, _c32(ln2w), _c32(ln2b), eps, adt, True, H2[i] if need else None)
             W1 = weight_cache.get(w1, adt)
-            if FUSE_GELU and adt == torch.bfloat16 and gemm.FUSE_GELU and gemm.dma_supported(h2, W1):
-                # fc1 + bias + GELU in the product's epilogue (widths 192 / 384: N % 192 == 0, K % 64 == 0); the pre-activation is
-                # written only when a backward follows
-                f, g = gemm.linear_gelu_dma(h2, W1, _c32(b1), f_out=torch.empty(R, 4 * C, dtype=adt, device=dev) if need else None,
-                                            g_out=GG[i] if need else None, bm=gemm.dma_bm(R))
-            else:
-                f = gemm.mm(h2, W1)
-                g = fused.bias_gelu_fwd(f, _c32(b1), adt, g=GG[i] if need else None)
+            # fc1 + bias + GELU in the product's epilogue (widths 192 / 384), else split; f is written only when a backward follows
+            f, g = gemm.mm_gelu(h2, W1, _c32(b1), need, g_out=GG[i] if need else None, tiled=False, fuse=FUSE_GELU)
             y, yb, rs, s = gemm.mm(g, weight_cache.get(w2, adt)), _c32(b2), dp2, s2
             if need:
                 saved += [s1, m1, r1, qkv, lse, s2, m2, r2, f]
@@ -164,12 +158,11 @@ class MaskedStackFn(torch.autograd.Function):
         # column-sum partials of every LayerNorm site (2i: LN1 of block i, 2i+1: LN2, 2 nblk: the tail) and every GELU site
         PLN = torch.empty(2 * nblk + 1, lib.gm3d_ln_plain_partial_rows(R), 3 * C, dtype=torch.float32, device=dev)
         SLN = torch.empty(2 * nblk + 1, 3 * C, dtype=torch.float32, device=dev)
-        W2T, WPT, W1T, WQT = gemm.stacked_transposes(
-            [[weight_cache.get(params[i * PER_BLOCK + k], adt) for i in range(nblk)] for k in (9, 3, 7, 2)])
+        ws = [[weight_cache.get(params[i * PER_BLOCK + k], adt) for i in range(nblk)] for k in (9, 3, 7, 2)]
+        W2T, WPT, W1T, WQT = gemm.stacked_transposes(ws)
         # fc2's input gradient x GELU'(f + b1) + fc1's bias-gradient partials in the product's epilogue where the tile shape allows
-        dma_bwd = FUSE_GELU and adt == torch.bfloat16 and gemm.FUSE_GELU_BWD and gemm.dma_supported(gin, W2T[0])
-        bm_bwd = gemm.dma_bm(R)
-        PGL = torch.empty(nblk, (R + bm_bwd - 1) // bm_bwd if dma_bwd else lib.gm3d_gelu_partial_rows(R), 4 * C, dtype=torch.float32, device=dev)
+        gelu_bwd = gemm.route_gelu_bwd(gin, ws[0][0], tiled=False, fuse=FUSE_GELU)
+        PGL = torch.empty(nblk, gelu_bwd[2], 4 * C, dtype=torch.float32, device=dev)
         SGL = torch.empty(nblk, 4 * C, dtype=torch.float32, device=dev)
         G = _add_ln_bwd(None, gin, None, None, None, None, meta["dp"][nblk - 1][1], T, DO[nblk - 1], PLN[2 * nblk], adt)
         db2 = SLN[2 * nblk, 2 * C:]
@@ -179,11 +172,7 @@ class MaskedStackFn(torch.autograd.Function):
             s1, m1, r1, qkv, lse, s2, m2, r2, f = saved[i * 9:(i + 1) * 9]
             gi = grads[i * PER_BLOCK:(i + 1) * PER_BLOCK]
             gi[10] = db2
-            if dma_bwd:
-                gemm.linear_gelu_bwd_dma(DO[i], W2T[i], f, _c32(b1), DF[i], PGL[i], bm=bm_bwd)
-            else:
-                dg = gemm.mm(DO[i], W2T[i])
-                fused.bias_gelu_bwd(dg, f, _c32(b1), adt, df=DF[i], partial=PGL[i])
+            gemm.mm_gelu_bwd(DO[i], W2T[i], f, _c32(b1), DF[i], PGL[i], gelu_bwd)
             gi[8] = SGL[i]
             dh2 = gemm.mm(DF[i], W1T[i])
             G = _add_ln_bwd(dh2, G, s2, m2, r2, _c32(ln2w), meta["dp"][i][0], T, DP[i], PLN[2 * i + 1], adt)

@@ -386,7 +386,18 @@ for _M in (77, 200):
             df2 = torch.empty_like(df)
             cp2 = torch.empty(-(-M // 64), Hd, dtype=torch.float32, device="cuda")
             gemm.linear_gelu_bwd_dma(d_o, w2t, f, b1, df2, cp2, bm=64)
-            return f, gl, g2, fd, gd, df, colpart.sum(0), df2, cp2.sum(0)
+            outs = [f, gl, g2, fd, gd, df, colpart.sum(0), df2, cp2.sum(0)]
+            # the same products through the dispatcher: what route_gelu / route_gelu_bwd name for each stack (tiled: TransformerStackFn's
+            # rule) and under the switches that send them to the tiled and the split forms
+            for tiled, sw in [(True, {}), (True, {"USE_DMA": False}), (False, {}), (False, {"USE_DMA": False})]:
+                with _switch(gemm, **sw):
+                    outs.append(gemm.mm_gelu(x, w1, b1, True, tiled=tiled))
+                    outs.append(gemm.mm_gelu(x, w1, b1, False, tiled=tiled)[1])
+                    route = gemm.route_gelu_bwd(d_o, w2t.t(), tiled=tiled)
+                    cp = torch.empty(route[2], Hd, dtype=torch.float32, device="cuda")
+                    outs += [gemm.mm_gelu_bwd(d_o, w2t, f, b1, torch.empty_like(df), cp, route), cp.sum(0)]
+            assert [gemm.route_gelu(x, w1, tiled=t)[0] for t in (True, False)] == ["dma", "dma"]
+            return outs
         return run
 
 
@@ -407,6 +418,9 @@ for _groups, _gr, _K, _N, _after, _rows in [(37, 32, 128, 256, False, True), (37
 
         def run():
             outs = [gemm.linear_pool(x, w, b, bias_after_pool=after, want_rows=rows, group_rows=gr)]
+            route = gemm.route_pool(x, w, gr)
+            assert route[0] == ("ws16" if gr == 16 else "ws" if M >= 32768 else "dma")
+            outs.append(gemm.linear_pool(x, w, b, bias_after_pool=after, want_rows=rows, group_rows=gr, route=route))
             if gr == 32 and M < 32768:
                 with _switch(gemm, POOL_ON_DMA=False):
                     outs.append(gemm.linear_pool(x, w, b, bias_after_pool=after, want_rows=rows))
