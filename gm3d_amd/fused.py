@@ -15,15 +15,14 @@ bias / gamma / beta gradient as fused column sums.  The residual stream is fp32,
 """
 import weakref
 
-import contextlib
-
 import torch
 
 from ._capi import lib
-from . import attention_pad, gemm
+from . import attention_pad, gemm, wgrads
 from . import streams as _streams
 from .gemm import bias_gelu_bwd, bias_gelu_fwd  # noqa: F401  (their home is beside the products they follow)
 from .ops import _launch, _ptr, _stream, _DT
+from .wgrads import async_wgrad, defer_wgrad  # noqa: F401  (INTEGRATION.md and the engines name them here)
 
 LNC = 384
 
@@ -205,100 +204,6 @@ def _attention_bwd(qkv, out, dout, lse, B, T, H, scale, dqkv=None):
     _launch("gm3d_attention_bwd", {"B": B, "T": T, "H": H, "dtype": str(qkv.dtype)}, lib.gm3d_attention_bwd, _ptr(qkv),
             _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), B, T, H, float(scale), _DT[qkv.dtype], _stream())
     return dqkv
-
-
-WGRAD_MIN_BLOCKS = 5      # stacks with fewer blocks (the 4-block decoders) DEFER their weight-gradient GEMMs to the deep stack's fork point
-_ASYNC_WGRAD = {"stream": None, "used": False, "min_blocks": 5, "deferred": []}
-
-
-def _wgrad_many(reqs):
-    """[(dy, x, out slot | None), ...] -> [dW, ...]: one launch for all of them where the NT kernel takes every request
-    (gemm.wgrad_nt_multi), else one batched GEMM per request."""
-    if gemm.MULTI_WGRAD and len(reqs) > 1 and all(gemm.wgrad_multi_ok(dy, x, out) for dy, x, out in reqs):
-        if len(reqs) <= 16:
-            return gemm.wgrad_nt_multi(reqs)
-        res = []                      # the kernel takes 16 problems per launch: ceil(n / 16) launches of about equal size
-        per = -(-len(reqs) // -(-len(reqs) // 16))
-        for i in range(0, len(reqs), per):
-            chunk = reqs[i:i + per]
-            res += gemm.wgrad_nt_multi(chunk) if len(chunk) > 1 else [gemm.wgrad(*chunk[0])]
-        return res
-    return [gemm.wgrad(dy, x, out) for dy, x, out in reqs]
-
-
-def defer_wgrad(dy, x, w=None):
-    """dW (N,K) f32 = dy (R,N)^T @ x (R,K) for a layer OUTSIDE the block stacks (heads, positional MLP), w its weight parameter.
-    Inside the engine's backward region, when w has a slot in the optimizer's flat gradient buffer and no gradient yet (nothing will
-    read or add to the result before the region ends), the product joins the stacks' one-launch weight gradients and lands in the slot;
-    elsewhere, or when the kernel does not take the shape, it is computed now."""
-    reg = _ASYNC_WGRAD
-    if (reg["stream"] is not None and gemm.MULTI_WGRAD and (DEFER_HEAD_WGRAD or reg.get("defer_heads")) and w is not None and w.is_leaf and w.grad is None
-            and dy.dim() == 2
-            and dy.is_contiguous() and x.is_contiguous()):
-        from .optim import grad_slots, ENABLE_DIRECT_WGRAD
-        slot = grad_slots.get(w) if ENABLE_DIRECT_WGRAD else None
-        if slot is not None and slot.is_contiguous() and slot.numel() == dy.shape[1] * x.shape[1]:
-            out = slot.view(1, dy.shape[1], x.shape[1])
-            if gemm.wgrad_multi_ok(dy.unsqueeze(0), x.unsqueeze(0), out):
-                reg["deferred"].append(((dy, x), [(dy.unsqueeze(0), x.unsqueeze(0), out)]))
-                return out[0]
-    return gemm.wgrad(dy, x)
-
-
-DEFER_HEAD_WGRAD = False  # the heads' / positional MLP's weight gradients inside the stacks' one-launch form (fused.defer_wgrad): measured
-#                           0.4 % slower (7.43 vs 7.39 ms same-box): three small products are cheaper where they stand than as extra tiles there
-
-
-def _run_deferred(reg, own=()):
-    """the deferred stacks' weight-gradient requests, plus `own` (the calling stack's), on the current stream -> the results of `own`"""
-    jobs, reg["deferred"] = reg["deferred"], []
-    cur = torch.cuda.current_stream()
-    reqs = []
-    for tensors, rq in jobs:
-        for t in tensors:
-            t.record_stream(cur)
-        reqs += rq
-    res = _wgrad_many(reqs + list(own)) if (reqs or own) else []
-    return res[len(reqs):]
-
-_wgrad_streams = {}
-ASYNC_WGRAD = True       # (tests flip it)
-
-
-class async_wgrad:
-    """with async_wgrad(device): <backward>  -- weight-gradient GEMMs of the deep block stacks run on a side stream during the
-    region; on exit the current stream waits for it (so whatever follows -- gradient gather, all-reduce, optimizer -- sees them)."""
-
-    def __init__(self, device, min_blocks=None, defer_heads=False):
-        """defer_heads: weight gradients of layers outside the block stacks (fused.defer_wgrad: token embeds, heads, positional MLPs)
-        join ONE launch at the region's exit -- for a model with many small such layers (Point-M2AE: 19) that is 2 launches instead
-        of 38; for the north-star model's three it measured slower (DEFER_HEAD_WGRAD)."""
-        self.dev, self.min_blocks = torch.device(device), (WGRAD_MIN_BLOCKS if min_blocks is None else min_blocks)
-        self.defer_heads = bool(defer_heads)
-
-    def __enter__(self):
-        if ASYNC_WGRAD and self.dev.type == "cuda":
-            key = (self.dev.type, self.dev.index)
-            if key not in _wgrad_streams:
-                _wgrad_streams[key] = torch.cuda.Stream(device=self.dev)
-            _ASYNC_WGRAD.update(stream=_wgrad_streams[key], used=False, min_blocks=self.min_blocks, defer_heads=self.defer_heads)
-            if self.defer_heads:
-                gemm.prepare_transposes()       # the small layers' transposed weight shadows: one launch per eight, not one per layer
-        return self
-
-    def __exit__(self, *exc):
-        reg = _ASYNC_WGRAD
-        ws, used = reg["stream"], reg["used"]
-        if reg.get("defer_heads"):
-            gemm.drop_transposes()
-        reg.update(stream=None, used=False, defer_heads=False)
-        if reg["deferred"]:                 # no deep stack came by to take them along: run them here, in line
-            if exc[0] is None:
-                _run_deferred(reg)
-            reg["deferred"] = []
-        if ws is not None and used:
-            _streams.join(ws)
-        return False
 
 
 DIRECT_INPUT_GRADS = True   # the stack backward writes dx / dpos in the activation type itself (no converting copies)
@@ -516,42 +421,10 @@ class TransformerStackFn(torch.autograd.Function):
             grads[i * PER_BLOCK:(i + 1) * PER_BLOCK] = gi
         finish_batched(PLN, SLN.view(2 * nblk + 1, 3 * C))
         finish_batched(PGL, SGL)
-        # all weight gradients of the stack: 4 batched GEMMs
-        # ... written straight into the parameters' slots of the optimizer's flat gradient buffer when the same-kind weights of
-        # the stack are adjacent there (optim._kind_key): autograd then adopts the slot views as .grad, nothing is copied later
-        from .optim import grad_slots
-        def slot(k):     # only when no gradient has been accumulated into these parameters yet (the slot is overwritten)
-            ps = [params[i * PER_BLOCK + k] for i in range(nblk)]
-            return grad_slots.stacked(ps) if dev.type == "cuda" and all(p.grad is None for p in ps) else None
-        # Inside an `async_wgrad` region (the engine's backward) the weight-gradient GEMMs leave the main stream:
-        #  * the 12-block encoder's four go to a side stream at once: what follows them in the backward is the mini-PointNet's
-        #    streaming (HBM-bound) passes, which leave the matrix cores idle;
-        #  * the shallow decoders' are DEFERRED to that same point (beside the encoder's latency-bound input-gradient chain, which
-        #    comes right after them, they cost 3.7 %): possible because their destinations are slots of the flat gradient buffer,
-        #    so the views handed to autograd now are filled later.  The region's exit runs whatever is still deferred and joins.
-        reg = _ASYNC_WGRAD
-        fresh = dev.type == "cuda" and all(params[i * PER_BLOCK + k].grad is None for i in range(nblk) for k in (9, 7, 3, 2))
-        ws = reg["stream"] if fresh else None
-        slots = [slot(k) for k in (9, 7, 3, 2)] if fresh else [None] * 4
-        jobs = [(DO, GG), (DF, H2), (DP, A), (DQ, H1)]
-        own = [(dy_, x_, sl) for (dy_, x_), sl in zip(jobs, slots)]
-        if ws is not None and nblk < reg["min_blocks"] and all(sl is not None for sl in slots):
-            reg["deferred"].append(((DO, GG, DF, H2, DP, A, DQ, H1), own))
-            gw2, gw1, gwp, gwq = slots
-        else:
-            if ws is not None and nblk >= reg["min_blocks"]:
-                _streams.fork(ws, who="fused.TransformerStackFn.backward: weight-gradient stream (async_wgrad region)")
-                reg["used"] = True
-                for t in (DO, GG, DF, H2, DP, A, DQ, H1):
-                    t.record_stream(ws)
-            else:
-                ws = None
-            with (torch.cuda.stream(ws) if ws is not None else contextlib.nullcontext()):
-                # the deferred decoders' requests and this stack's own: ONE launch (+ one slab sum) where the kernel takes them all
-                gw2, gw1, gwp, gwq = _run_deferred(reg, own) if ws is not None else _wgrad_many(own)
-        for i in range(nblk):
-            grads[i * PER_BLOCK + 9], grads[i * PER_BLOCK + 7] = gw2[i], gw1[i]
-            grads[i * PER_BLOCK + 3], grads[i * PER_BLOCK + 2] = gwp[i], gwq[i]
+        # all weight gradients of the stack: 4 batched GEMMs, forked to the side stream or deferred inside an async_wgrad region
+        grads[9::PER_BLOCK], grads[7::PER_BLOCK], grads[3::PER_BLOCK], grads[2::PER_BLOCK] = wgrads.stack(
+            [(DO, GG, params[9::PER_BLOCK]), (DF, H2, params[7::PER_BLOCK]), (DP, A, params[3::PER_BLOCK]), (DQ, H1, params[2::PER_BLOCK])],
+            takes_part=True)
         if last:
             return (dx_a.view(B, T, C), dpos_a.view(B, T, C), None, g_final_w, g_final_b) + tuple(grads)
         dx = G.view(B, T, C).to(ctx.in_dtypes[0])

@@ -2,7 +2,7 @@
 
     mm(x, w, bias, out)    x (M,K) @ w (N,K)^T (+ bias)   `route` names the target, `_tn` launches it
     mm_nn(x, w, out)       x (M,N) @ w (N,K): a layer's input gradient, the TN product against a transposed copy of w
-    wgrad(dy, x, out)      dy^T @ x in fp32: a layer's (2-D) or a whole stack's (batched) weight gradient
+    wgrad(dy, x, out)      dy^T @ x in fp32: a layer's (2-D) or a stack's (batched) weight gradient (`route_wgrad`; wgrads.py schedules them)
 
 bf16 operands in the kernels' layout (`_rows_ok`) run on the hand-written MFMA kernels: csrc/gemm.hip (register prefetch, ragged
 widths), gemm_ring.hip (LDS-DMA ring), gemm_dma.hip (LDS-DMA double buffer, bm x bn tiles), gemm_ws.hip (weight-stationary, tall
@@ -539,9 +539,13 @@ OWN_WGRAD = True          # weight-gradient (NT) GEMMs on the hand-written kerne
 
 def wgrad_supported(dy, x):
     """dy (nb,R,N), x (nb,R,K) bf16 with unit inner stride and a common batch layout; N, K % 8 == 0 (ragged edge tiles), R % 32 == 0."""
-    edge = 8 if RAGGED else 128
-    return (ENABLED and OWN_WGRAD and _rows_ok(dy, edge, 3) and _rows_ok(x, edge, 3) and dy.shape[:2] == x.shape[:2]
-            and dy.shape[1] % 32 == 0 and (dy.shape[0] == 1 or (dy.stride(0) % 8 == 0 and x.stride(0) % 8 == 0)))
+    return _rows_ok(dy, 8 if RAGGED else 128, 3) and _wgrad_x_ok(x, dy.shape[0], dy.shape[1], dy.stride(0))
+
+
+def _wgrad_x_ok(x, nb, R, dy_stride):
+    """wgrad_supported's conditions on everything but dy's own layout (route_wgrad asks them for a padded copy of dy it has not made)"""
+    return (ENABLED and OWN_WGRAD and _rows_ok(x, 8 if RAGGED else 128, 3) and x.shape[:2] == (nb, R) and R % 32 == 0
+            and (nb == 1 or (dy_stride % 8 == 0 and x.stride(0) % 8 == 0)))
 
 
 FUSE_SLAB_SUM = False      # the sum over the row splits inside the NT launch (the last workgroup of a tile adds its slabs in slab order):
@@ -632,30 +636,19 @@ def wgrad_multi_ok(dy, x, out):
                                  and (nb == 1 or out.stride(0) >= N * K) and out.data_ptr() % 16 == 0)))
 
 
-def wgrad_nt_multi(reqs, splits=None, want_splits=False):
-    """[(dy (nb,R,N), x (nb,R,K), out (nb,N,K) f32 | None), ...] (at most 16) -> [out, ...]: every product dy[b]^T @ x[b] of every request
-    in ONE launch of the 128 x 128-tile weight-gradient kernel, then ONE launch that adds the row-split slabs (csrc/gemm_nt.hip
-    gm3d_gemm_nt_bf16_multi).  Bit-identical to wgrad_nt per request with the same row splits (splits=: one per request; default: each
-    request's own choice, capped by MULTI_SPLITS_MAX when the launch is large).
-    NOTE: the DEFAULT splits of a request depend on the composition of the whole launch (its total tile count), and the
-    fp32 summation order of a weight gradient follows its splits.  The same product batched differently -- a stack alone, with the
-    deferred decoders, inside SegmentedDDPStep's cut, per-request fallback beyond 16 -- may therefore differ in the last bits
-    (tests/test_gpu_gemm.py::test_wgrad_multi_default_splits_depend_on_the_batch_only_in_the_last_bits pins the size of that: 1e-6)."""
-    n = len(reqs)
-    VP, I, LL = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_longlong * n
-    outs, parts, spl = [], [], []
-    tiles = [r[0].shape[0] * ((r[0].shape[2] + 127) // 128) * ((r[1].shape[2] + 127) // 128) for r in reqs]
+def multi_splits(problems, splits=None):
+    """[(nb, R, N, K), ...] -> the row splits of each request of ONE wgrad_nt_multi launch (`splits` given: those).  Pure: the shapes,
+    the switches above and gm3d_gemm_nt_splits (host code).  The DEFAULT splits of a request depend on the composition of the whole
+    launch (DESIGN.md 3b')."""
+    if splits is not None:
+        return list(splits)
+    tiles = [nb * ((N + 127) // 128) * ((K + 127) // 128) for nb, _, N, K in problems]
     tiles_all = sum(tiles)
-    rows_target = max(512, sum(t_ * r[0].shape[1] for t_, r in zip(tiles, reqs)) // MULTI_TARGET_WGS)
-    for dy, x, out in reqs:
-        nb, R, N = dy.shape
-        K = x.shape[2]
-        if out is None:
-            out = torch.empty(nb, N, K, dtype=torch.float32, device=dy.device)
+    rows_target = max(512, sum(t_ * p[1] for t_, p in zip(tiles, problems)) // MULTI_TARGET_WGS)
+    spl = []
+    for nb, R, N, K in problems:
         s_ = lib.gm3d_gemm_nt_splits(nb, R, N, K)
-        if splits is not None:
-            s_ = splits[len(spl)]
-        elif MULTI_SPLITS_MAX and tiles_all < 768:
+        if MULTI_SPLITS_MAX and tiles_all < 768:
             # few tiles in all (the mini-PointNet's products: 2-12 tiles each over 8192 .. 262,144 rows): splits per problem in
             # proportion to its rows, so that the launch has ~512 workgroups of about equal length (each problem on its own would cut
             # itself into 64 slabs to fill the chip alone)
@@ -668,14 +661,26 @@ def wgrad_nt_multi(reqs, splits=None, want_splits=False):
             s_ = min(s_, MULTI_SPLITS_MAX if R > 4096 else 1)
             while s_ > 1 and R % (32 * s_):
                 s_ -= 1
-        outs.append(out)
         spl.append(s_)
-        parts.append(torch.empty(nb, s_, N, K, dtype=torch.float32, device=dy.device) if s_ > 1 else None)
-    _launch("gm3d_gemm_nt_bf16_multi", {"count": n, "problems": [(r[0].shape[0], r[0].shape[1], r[0].shape[2], r[1].shape[2]) for r in reqs],
-                                        "splits": list(spl)}, lib.gm3d_gemm_nt_bf16_multi, n,
+    return spl
+
+
+def wgrad_nt_multi(reqs, splits=None, want_splits=False):
+    """[(dy (nb,R,N), x (nb,R,K), out (nb,N,K) f32 | None), ...] (at most 16) -> [out, ...]: every product dy[b]^T @ x[b] of every request
+    in ONE launch of the 128 x 128-tile weight-gradient kernel, then ONE launch that adds the row-split slabs (csrc/gemm_nt.hip
+    gm3d_gemm_nt_bf16_multi).  Bit-identical to wgrad_nt per request with the same row splits (splits=: one per request; default:
+    `multi_splits`, each request's own choice, capped by MULTI_SPLITS_MAX when the launch is large)."""
+    n = len(reqs)
+    VP, I, LL = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_longlong * n
+    problems = [(dy.shape[0], dy.shape[1], dy.shape[2], x.shape[2]) for dy, x, _ in reqs]
+    spl = multi_splits(problems, splits)
+    f32 = dict(dtype=torch.float32, device=reqs[0][0].device)
+    outs = [torch.empty(nb, N, K, **f32) if r[2] is None else r[2] for r, (nb, _, N, K) in zip(reqs, problems)]
+    parts = [torch.empty(nb, s_, N, K, **f32) if s_ > 1 else None for (nb, _, N, K), s_ in zip(problems, spl)]
+    _launch("gm3d_gemm_nt_bf16_multi", {"count": n, "problems": problems, "splits": list(spl)}, lib.gm3d_gemm_nt_bf16_multi, n,
             VP(*[_ptr(r[0]) for r in reqs]), VP(*[_ptr(r[1]) for r in reqs]), VP(*[_ptr(o) for o in outs]),
-            VP(*[(_ptr(p) if p is not None else None) for p in parts]), I(*[r[0].shape[0] for r in reqs]), I(*[r[0].shape[1] for r in reqs]),
-            I(*[r[0].shape[2] for r in reqs]), I(*[r[1].shape[2] for r in reqs]), I(*[r[0].stride(1) for r in reqs]),
+            VP(*[(_ptr(p) if p is not None else None) for p in parts]), I(*[p[0] for p in problems]), I(*[p[1] for p in problems]),
+            I(*[p[2] for p in problems]), I(*[p[3] for p in problems]), I(*[r[0].stride(1) for r in reqs]),
             I(*[r[1].stride(1) for r in reqs]), LL(*[r[0].stride(0) for r in reqs]), LL(*[r[1].stride(0) for r in reqs]),
             LL(*[o.stride(0) for o in outs]), I(*spl), _stream())
     return (outs, spl) if want_splits else outs
@@ -703,12 +708,44 @@ def _bmm_f32(dy, x, out=None):
     return r if out is None else out.copy_(r)
 
 
-def _wgrad_lib(dy, x, out, flat):
+def _wgrad_lib(dy, x, out, S, adder):
     """wgrad on the library (shapes the NT kernels do not take).  Long reductions over few output tiles fill a fraction of the 256 CUs:
-    the rows are cut S ways into more batches and the S partial products added in order by our own kernel.  S and the adding kernel
-    are each caller shape's own: SPLITK for one layer's rows (flat), WGRAD_ROW_SPLIT for a stack."""
+    the rows are cut S ways into more batches and the S partial products added in order by our own kernel `adder` (route_wgrad)."""
     nb, R, N = dy.shape
     K = x.shape[2]
+    if S == 1:
+        return _bmm_f32(dy, x, out)
+    part = _bmm_f32(dy.view(nb * S, R // S, N), x.view(nb * S, R // S, K))
+    if out is None:
+        out = torch.empty(nb, N, K, dtype=torch.float32, device=dy.device)
+    tail = {"gm3d_sum_few_rows": (nb, S, N * K, _ptr(out)), "gm3d_colsum_finish": (S, N * K, N * K, _ptr(out), 0),
+            "gm3d_colsum_finish_batched": (nb, S * N * K, S, N * K, N * K, _ptr(out), N * K)}[adder]
+    _launch(adder, {"rows": nb * S, "cols": N * K}, getattr(lib, adder), _ptr(part), *tail, _stream())
+    return out
+
+
+def route_wgrad(dy, x, out=None):
+    """What runs dW = dy^T @ x into `out` -> (kind, launch arguments), for wgrad's 2-D and batched forms.  In this order: "nt" with
+    `splits` (csrc/gemm_nt.hip), "f32" (the fp32 NT kernel under F32_OWN, csrc/gemm_f32.hip), "pad" with `splits` (one narrow bf16
+    layer -- the 96-wide reconstruction head where the ragged widths are off -- with dy zero-padded to one 128-column tile), "lib"
+    with the row-chunk count `S` and `adder`, the kernel that adds the chunks (None for S = 1): S and the adding kernel are each caller
+    shape's own, SPLITK for one layer's rows (2-D), WGRAD_ROW_SPLIT for a stack.  Reads shapes, strides, dtypes, addresses and the
+    module switches only: nothing is launched or allocated."""
+    flat = dy.dim() == 2
+    if flat:
+        plain = dy.is_contiguous() and x.is_contiguous()
+        dy, x = dy.unsqueeze(0), x.unsqueeze(0)
+    nb, R, N = dy.shape
+    K = x.shape[2]
+    if not flat:
+        plain = out is None or (out.stride(2) == 1 and out.stride(1) == K and out.stride(0) == N * K)
+    if plain and wgrad_supported(dy, x):
+        return "nt", {"splits": lib.gm3d_gemm_nt_splits(nb, R, N, K)}
+    if f32_own(dy) and x.dtype == torch.float32:
+        return "f32", {}
+    # (the padded copy of dy would be a fresh, aligned (1, R, 128) bf16 tensor on dy's device: _rows_ok by construction)
+    if flat and plain and 0 < N < 128 and dy.dtype == torch.bfloat16 and dy.is_cuda and _wgrad_x_ok(x, 1, R, 0):
+        return "pad", {"splits": lib.gm3d_gemm_nt_splits(1, R, 128, K)}          # (the library runs this shape on 32x32 tiles: 88 us per step)
     if flat:
         S = SPLITK if R % SPLITK == 0 and R >= 64 * SPLITK else 1
     else:
@@ -721,45 +758,29 @@ def _wgrad_lib(dy, x, out, flat):
             S = 1
         if not (R % S == 0 and dy.is_contiguous() and x.is_contiguous()):
             S = 1
-    if S == 1:
-        return _bmm_f32(dy, x, out)
-    part = _bmm_f32(dy.view(nb * S, R // S, N), x.view(nb * S, R // S, K))
-    if out is None:
-        out = torch.empty(nb, N, K, dtype=torch.float32, device=dy.device)
-    if SUM_FEW_ROWS:
-        _launch("gm3d_sum_few_rows", {"rows": nb * S, "cols": N * K}, lib.gm3d_sum_few_rows, _ptr(part), nb, S, N * K, _ptr(out), _stream())
-    elif flat:
-        _launch("gm3d_colsum_finish", {"rows": S, "cols": N * K}, lib.gm3d_colsum_finish, _ptr(part), S, N * K, N * K, _ptr(out), 0, _stream())
-    else:
-        _launch("gm3d_colsum_finish_batched", {"rows": nb * S, "cols": N * K}, lib.gm3d_colsum_finish_batched, _ptr(part), nb, S * N * K, S,
-                N * K, N * K, _ptr(out), N * K, _stream())
-    return out
+    few = "gm3d_sum_few_rows" if SUM_FEW_ROWS else "gm3d_colsum_finish" if flat else "gm3d_colsum_finish_batched"
+    return "lib", {"S": S, "adder": few if S > 1 else None}
 
 
 def wgrad(dy, x, out=None):
     """dW = dy^T @ x in fp32: dy (R,N), x (R,K) -> (N,K), one layer's weight gradient; or dy (nb,R,N), x (nb,R,K) -> (nb,N,K), every
-    block of a stack at once, into `out` (the parameters' slots of the optimizer's flat gradient buffer) when given.  In this order:
-    the NT kernel (csrc/gemm_nt.hip), the fp32 NT kernel under F32_OWN (csrc/gemm_f32.hip), for one narrow bf16 layer (the 96-wide
-    reconstruction head where the ragged widths are off) dy zero-padded to one 128-column tile, the library."""
+    block of a stack at once, into `out` (the parameters' slots of the optimizer's flat gradient buffer) when given.  On what
+    `route_wgrad` names."""
+    kind, args = route_wgrad(dy, x, out)
     flat = dy.dim() == 2
     if flat:
-        plain = dy.is_contiguous() and x.is_contiguous()
         dy, x = dy.unsqueeze(0), x.unsqueeze(0)
-    nb, R, N = dy.shape
-    K = x.shape[2]
-    if not flat:
-        plain = out is None or (out.stride(2) == 1 and out.stride(1) == K and out.stride(0) == N * K)
-    if plain and wgrad_supported(dy, x):
-        r = wgrad_nt(dy, x, out)
-    elif f32_own(dy) and x.dtype == torch.float32:
+    if kind == "nt":
+        r = wgrad_nt(dy, x, out, **args)
+    elif kind == "f32":
         r = wgrad_nt_f32(dy, x, out)
-    elif flat and plain and 0 < N < 128 and dy.dtype == torch.bfloat16 and wgrad_supported(dy.new_empty(1, R, 128), x):
-        # (the library runs this shape on 32x32 tiles: 88 us per step)
-        pad = torch.zeros(1, R, 128, dtype=dy.dtype, device=dy.device)
+    elif kind == "pad":
+        N = dy.shape[2]
+        pad = torch.zeros(1, dy.shape[1], 128, dtype=dy.dtype, device=dy.device)
         pad[:, :, :N] = dy
-        r = wgrad_nt(pad, x)[:, :N].contiguous()
+        r = wgrad_nt(pad, x, None, **args)[:, :N].contiguous()
     else:
-        r = _wgrad_lib(dy, x, out, flat)
+        r = _wgrad_lib(dy, x, out, **args)
     return r[0] if flat else r
 
 

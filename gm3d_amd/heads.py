@@ -13,13 +13,9 @@ import torch
 
 from ._capi import lib
 from .embed import _c32, _finish, colsum, linear_bias
-
-
-def _defer_wgrad(dy, x, w=None):
-    from . import fused
-    return fused.defer_wgrad(dy, x, w)
 from .fused import weight_cache
 from . import gemm
+from .wgrads import defer_wgrad
 from .ops import _launch, _ptr, _stream, _DT
 
 
@@ -73,7 +69,7 @@ class LinearBiasFn(torch.autograd.Function):
                 dW = gemm.wgrad(pad, x2)[:N].contiguous().reshape(w.shape)
                 return dx, dW, db, None
             dx = gemm.mm_nn(dy2, W).view(ctx.shp).to(ctx.xdt)
-            dW = _defer_wgrad(dy2, x2, w).reshape(w.shape)
+            dW = defer_wgrad(dy2, x2, w).reshape(w.shape)
             return dx, dW, db, None
 
 
@@ -432,7 +428,7 @@ class PosEmbedFn(torch.autograd.Function):
             B, G, R, C = ctx.dims
             d = dout.reshape(R, -1).to(adt).contiguous()
             W1 = weight_cache.get(w1, adt)
-            dW1 = _defer_wgrad(d, h, w1)
+            dW1 = defer_wgrad(d, h, w1)
             db1 = colsum(d, adt)
             dh = gemm.mm_nn(d, W1).contiguous()
             nrows = lib.gm3d_embed_partial_rows(3, R, C)
@@ -534,7 +530,7 @@ class LossPredHeadFn(torch.autograd.Function):
                     _ptr(dy), _ptr(dt), G, K, C, float(slope), _DT[adt], _stream())
             W0 = weight_cache.get(w0, adt).reshape(C, Cin)
             dx = gemm.mm_nn(dy, W0).view(B, L, Cin).to(ctx.xdt)
-            dW0 = _defer_wgrad(dy, x2, w0).reshape(w0.shape)
+            dW0 = defer_wgrad(dy, x2, w0).reshape(w0.shape)
             db0 = colsum(dt, torch.float32)
             return dx, dW0, db0, s2, s1, dW1, db1, None, None, None, None
 

@@ -23,7 +23,7 @@ attention sees the same allowed keys in the same relative order); filler rows ar
 import torch
 
 from ._capi import lib
-from . import fused, gemm
+from . import fused, gemm, wgrads
 from .embed import _c32
 from .fused import PER_BLOCK, block_params, weight_cache  # noqa: F401
 from .ops import _DT, _launch, _ptr, _stream, launch_masked_attention
@@ -187,17 +187,10 @@ class MaskedStackFn(torch.autograd.Function):
             grads[i * PER_BLOCK:(i + 1) * PER_BLOCK] = gi
         fused.finish_batched(PLN, SLN)
         fused.finish_batched(PGL, SGL)
-        # all weight gradients of the stack: ONE launch, into the parameters' slots of the flat gradient buffer where they are
-        # adjacent there (optim._kind_key) and hold no gradient yet
-        from .optim import grad_slots
-
-        def slot(k):
-            ps = [params[i * PER_BLOCK + k] for i in range(nblk)]
-            return grad_slots.stacked(ps) if dev.type == "cuda" and all(p.grad is None for p in ps) else None
-        gw2, gw1, gwp, gwq = fused._wgrad_many([(DO, GG, slot(9)), (DF, H2, slot(7)), (DP, A, slot(3)), (DQ, H1, slot(2))])
-        for i in range(nblk):
-            grads[i * PER_BLOCK + 9], grads[i * PER_BLOCK + 7] = gw2[i], gw1[i]
-            grads[i * PER_BLOCK + 3], grads[i * PER_BLOCK + 2] = gwp[i], gwq[i]
+        # all weight gradients of the stack: ONE launch, now and on this stream also inside an async_wgrad region (takes_part=False)
+        grads[9::PER_BLOCK], grads[7::PER_BLOCK], grads[3::PER_BLOCK], grads[2::PER_BLOCK] = wgrads.stack(
+            [(DO, GG, params[9::PER_BLOCK]), (DF, H2, params[7::PER_BLOCK]), (DP, A, params[3::PER_BLOCK]), (DQ, H1, params[2::PER_BLOCK])],
+            takes_part=False)
         for j, (gr, p) in enumerate(zip(grads, params)):
             if gr is not None and gr.dtype != p.dtype:
                 grads[j] = gr.to(p.dtype)

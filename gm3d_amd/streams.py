@@ -6,7 +6,7 @@ capture.  The runtime is specified to return an error for it; on this stack it t
 `torch.cuda.graphs.capture_end` -- no Python error, the test run simply died.  The product forks side streams in four places
 (the decoders' second branch, the EMA teacher's parallel chains, the weight-gradient stream of a backward region, the data-
 parallel step's warm-up), some of them nested (a stack node running ON the decoders' side stream forks the weight-gradient
-stream), and switches (`fused.ASYNC_WGRAD`, `NOGRAD_SPLIT`, `GM3D_PARALLEL_DECODERS`) recombine them.
+stream), and switches (`wgrads.ASYNC_WGRAD`, `NOGRAD_SPLIT`, `GM3D_PARALLEL_DECODERS`) recombine them.
 
     fork(side, who=...)      side waits for the current stream; booked as open while a capture is being audited
     join(side)               the current stream waits for side; booked as closed.  Joining INTO a stream that is itself a

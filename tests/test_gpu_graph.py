@@ -314,17 +314,17 @@ def test_inference_stack_split_equals_whole():
 
 def test_async_weight_gradients_equal_inline():
     """Inside the engine's backward the encoder's weight-gradient GEMMs run on a side stream and the decoders' are deferred to the
-    same point (fused.async_wgrad); the flat gradient buffer must be what the in-line order produces, eager and graph-captured."""
+    same point (wgrads.async_wgrad); the flat gradient buffer must be what the in-line order produces, eager and graph-captured."""
     from types import SimpleNamespace
-    from gm3d_amd import engine_pretrain as E, fused, models_mae_learn_loss as M
+    from gm3d_amd import engine_pretrain as E, models_mae_learn_loss as M, wgrads
     args = SimpleNamespace(mask_ratio=0.6, epochs=400, relative=True, bf16=True, accum_iter=1, lr=1e-3, min_lr=0.0, warmup_epochs=40)
     x = torch.randn(8, 1024, 3, device="cuda") * 0.3
     noise = torch.rand(8, 64, device="cuda")
     res = {}
-    was = fused.ASYNC_WGRAD
+    was = wgrads.ASYNC_WGRAD
     try:
         for on in (True, False):
-            fused.ASYNC_WGRAD = on
+            wgrads.ASYNC_WGRAD = on
             torch.manual_seed(0)
             model = M.mae_vit_base_patch16_dec512d8b().cuda().train()
             for m in model.modules():
@@ -338,10 +338,10 @@ def test_async_weight_gradients_equal_inline():
                 g = opt.G.clone()
                 E.step_update(model, ema, opt)
             torch.cuda.synchronize()
-            assert not fused._ASYNC_WGRAD["deferred"] and fused._ASYNC_WGRAD["stream"] is None
+            assert not wgrads.region.deferred and wgrads.region.stream is None and wgrads.current() is None
             res[on] = (g, opt.P.clone())
     finally:
-        fused.ASYNC_WGRAD = was
+        wgrads.ASYNC_WGRAD = was
     assert torch.equal(res[True][0], res[False][0]) and torch.equal(res[True][1], res[False][1])
 
 

@@ -148,7 +148,7 @@ def test_one_rank_segmented_step_equals_its_eager_form_and_the_single_backward()
     parameter's largest gradient: a segment's deferred weight gradients form their own one-launch batch, and the NT kernel's default
     row splits -- the fp32 summation order of a weight gradient -- depend on the whole launch's composition (gemm.wgrad_nt_multi);
     the sum at the enc[1] cut is the one the single backward forms (a + b in the activation type)."""
-    from gm3d_amd import fused
+    from gm3d_amd import wgrads
     from gm3d_amd import point_m2ae as P
     data = [clouds.gaussian(B, 2048, seed=120 + i).cuda() for i in range(4)]
     noise = [torch.rand(B, 64, generator=torch.Generator().manual_seed(130 + i)).cuda() for i in range(4)]
@@ -178,7 +178,7 @@ def test_one_rank_segmented_step_equals_its_eager_form_and_the_single_backward()
     pts, group, prop = staged()
     with torch.autocast("cuda", dtype=torch.bfloat16):
         out = P.pretrain_forward(m, ema.ema, pts, 100, args.epochs, mask_noise=noise[1], group=group, prop=prop)
-    with fused.async_wgrad(out["loss"].device, defer_heads=True):
+    with wgrads.async_wgrad(out["loss"].device, defer_heads=True):
         out["loss"].backward()
     opt.gather_grads()
     g_single = opt.G.clone()

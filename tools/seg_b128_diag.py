@@ -9,7 +9,7 @@ os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29655")
 torch.cuda.set_device(0)
 dist.init_process_group("gloo", rank=0, world_size=1)
 from gm3d_amd import engine_pretrain as E, models_mae_learn_loss as M, fused, gemm
-for item in os.environ.get("SET", "").split():        # SET="fused.ASYNC_WGRAD=False models_mae_learn_loss.PARALLEL_DECODERS=False"
+for item in os.environ.get("SET", "").split():        # SET="wgrads.ASYNC_WGRAD=False models_mae_learn_loss.PARALLEL_DECODERS=False"
     name, val = item.split("=")
     mod, attr = name.rsplit(".", 1)
     import importlib
