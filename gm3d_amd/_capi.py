@@ -5,167 +5,48 @@ import fails loudly, and every op rejects non-GPU tensors.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GM3D_HIP_LIB") or os.path.join(_HERE, "lib", "libgm3d_hip.so")
+HEADER = os.path.join(_HERE, "..", "include", "gm3d.h")
 
 GM3D_OK, GM3D_EINVAL, GM3D_EUNSUPPORTED, GM3D_ELAUNCH = 0, -1, -2, -3
 GM3D_F32, GM3D_BF16 = 0, 1
 
-_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+_CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
+           "gm3d_stream_t": ctypes.c_void_p}
+_DECL = re.compile(r"^([A-Za-z_][A-Za-z0-9_ ]*?\**) *\b(gm3d_[a-z0-9_]+)\s*\(([^;{()]*)\)\s*;", re.M)
 
-# name -> argtypes; mirrors include/gm3d.h one to one (tests/test_capi_symbols.py checks it)
-SIGNATURES = {
-    "gm3d_abi_version": [],
-    "gm3d_strerror": [_i],
-    "gm3d_fps": [_vp, _i, _i, _i, _vp, _vp, _vp],
-    "gm3d_gather_points": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "gm3d_gather_points_grad": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "gm3d_knn": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "gm3d_knn_group": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "gm3d_chamfer_fwd": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "gm3d_chamfer_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
-    "gm3d_patch_chamfer_loss_fwd": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
-    "gm3d_patch_chamfer_loss_bwd": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp],
-    "gm3d_attention_fwd": [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    "gm3d_attention_qkv_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "gm3d_attention_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    "gm3d_ln_plain_partial_rows": [_i],
-    "gm3d_ln_plain_fwd": [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "gm3d_ln_plain_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "gm3d_residual_ln_fwd": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "gm3d_residual_ln_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "gm3d_ln_partial_rows": [_i],
-    "gm3d_colsum_finish": [_vp, _i, _i, _i, _vp, _i, _vp],
-    "gm3d_colsum_finish_batched": [_vp, _i, ctypes.c_longlong, _i, _i, _i, _vp, _i, _vp],
-    "gm3d_bias_gelu_fwd": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "gm3d_bias_gelu_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "gm3d_gelu_partial_rows": [_i],
-    "gm3d_embed_partial_rows": [_i, _i, _i],
-    "gm3d_moments3": [_vp, _i, _vp, _vp],
-    "gm3d_pn_layer1_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "gm3d_group_max_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "gm3d_group_max_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "gm3d_bn_bcast_stats": [_vp, _vp, _i, _i, _i, _vp, _i, _vp],
-    "gm3d_bn_bcast_apply_relu": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    "gm3d_bn_bcast_bwd_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _i, _vp],
-    "gm3d_bn_bcast_bwd_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    "gm3d_head_fold": [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp],
-    "gm3d_head_rowdot": [_vp, _vp, _vp, _i, _i, _vp, _i, _vp],
-    "gm3d_head_fold_bwd": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp],
-    "gm3d_head_outer": [_vp, _vp, _i, _i, _vp, _i, _vp],
-    "gm3d_scale_translate": [_vp, _vp, _f, _f, _f, _i, _i, _vp],
-    "gm3d_group_select_maps": [_vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "gm3d_bn_bcast_apply_relu_sel": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    "gm3d_bn_bcast_bwd_stats_sel": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _i, _vp],
-    "gm3d_bn_bcast_bwd_apply_sel": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    "gm3d_lin3_gelu_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "gm3d_lin3_gelu_bwd": [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp],
-    "gm3d_lin3_finish": [_vp, _i, _i, _vp, _vp, _vp],
-    "gm3d_rank_loss": [_vp, _vp, _i, _i, _vp, _vp, _vp],
-    "gm3d_rank_loss_tail": [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    "gm3d_rank_loss_tail_bwd": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],
-    "gm3d_ema_counters": [_vp, _vp, _i, _f, _f, _vp],
-    "gm3d_drop_path_scales": [_vp, _vp, _i, _i, _vp, _vp],
-    "gm3d_pad_cols": [_vp, ctypes.c_longlong, _i, _i, _vp, _i, _i, _vp],
-    "gm3d_patch_chamfer_loss_bwd_full": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp],
-    "gm3d_mask_select_b": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
-    "gm3d_pn1_bwd_finalize": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
-    "gm3d_gemm_tn_bf16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_gelu": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_pool": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_gelu_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_res": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_lna": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tile_rows": [_i],
-    "gm3d_gemm_tn_bf16_ring": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_ws": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_ws_pool": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_ws_supported": [_i, _i, _i],
-    "gm3d_gemm_tn_bf16_ws_poolg": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_nt_bf16_sum": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i, _vp],
-    "gm3d_gemm_nt_tiles": [_i, _i],
-    "gm3d_gemm_nt_bf16_multi": [_i] + [_vp] * 14 + [_vp],
-    "gm3d_gemm_tn_bf16_ws_bn_apply": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_ws_bn_stats": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_ws_stats_rows": [_i, _i, _i],
-    "gm3d_gemm_tn_bf16_ws_bn_apply_g": [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_ws_bn_stats_g": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_ring96": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_dma": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_dma_gelu_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_dma_gelu": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_transpose_bf16_batched": [_vp, _vp, _i, _i, _i, ctypes.c_longlong, _vp],
-    "gm3d_transpose_bf16_multi": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "gm3d_token_assemble_fwd": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
-    "gm3d_token_assemble_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp],
-    "gm3d_sum_few_rows": [_vp, _i, _i, ctypes.c_longlong, _vp, _vp],
-    "gm3d_gemm_nt_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i,
-                          ctypes.c_longlong, _vp],
-    "gm3d_gemm_nt_bf16_big": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _i,
-                              ctypes.c_longlong, _vp],
-    "gm3d_gemm_nt_splits": [_i, _i, _i, _i],
-    "gm3d_radius_mask_bits": [_vp, _vp, _f, _i, _i, _vp, _vp],
-    "gm3d_radius_mask_bits_m": [_vp, _vp, _i, _f, _i, _i, _vp, _vp],
-    "gm3d_attention_masked_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "gm3d_attention_masked_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "gm3d_attention_long_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "gm3d_attention_long_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp],
-    "gm3d_mask_select": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
-    "gm3d_bn_finalize": [_vp, ctypes.c_double, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "gm3d_pn1_finalize": [_vp, ctypes.c_double, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "gm3d_flat_partial_rows": [ctypes.c_longlong],
-    "gm3d_adamw_ema_flat_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _f, _f, _f, _f,
-                                 _vp, _f, _vp, _vp, _vp, _vp],
-    "gm3d_adamw_ema_flat_step_lrd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, _vp, _f, _f,
-                                     _f, _f, _vp, _f, _vp, _vp, _vp, _vp],
-    "gm3d_group_scatter_add": [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp],
-    "gm3d_pn_layer1_bwd_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp],
-    "gm3d_colsum_finish_f64": [_vp, _i, _i, _i, _vp, _vp],
-    "gm3d_colsum_partial": [_vp, _i, _i, _vp, _i, _vp],
-    "gm3d_gather_inverse": [_vp, _i, _i, _i, _vp, _vp, _vp],
-    "gm3d_gather_rows_bwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "gm3d_add_ln_fwd": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "gm3d_add_ln_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "gm3d_add_ln_bwd_acc": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp],
-    "gm3d_partition_visible": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "gm3d_select_rows": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "gm3d_back_project": [_vp, _vp, _i, _i, _i, _i, _vp, _vp],
-    "gm3d_interp3_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gather_rows_bwd_w": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "gm3d_where_rows": [_vp, _i, _vp, _vp, _i, _vp, ctypes.c_longlong, _i, _i, _vp],
-    "gm3d_take_rows": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "gm3d_colsum_partial_w": [_vp, _vp, _i, _i, _vp, _i, _vp],
-    "gm3d_gemm_tn_bf16_dma_pool": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_gemm_tn_bf16_dmaw": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    "gm3d_vote_sample": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp],
-    "gm3d_cls_tail_vote": [_vp, _i, _i, _i, _i] + [_vp] * 14 + [_i, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp],
-    "gm3d_cls_tail_fwd": [_vp, _i, _i, _i, _i] + [_vp] * 10 + [_i] + [_vp] * 6 + [_f, _f, _i] + [_vp] * 8 + [_i, _vp],
-    "gm3d_cls_tail_bwd": [_i, _i, _i, _i] + [_vp] * 7 + [_i, _i] + [_vp] * 21 + [_i, _vp],
-    "gm3d_cls_tail_vote_pool": [_vp, _i, _i, _i, _i, _i] + [_vp] * 14 + [_i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
-    "gm3d_svm_gram": [_vp, _i, _i, _vp, _vp],
-    "gm3d_svm_smo": [_vp, _i, _i, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp],
-    "gm3d_svm_weights": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
-    "gm3d_svm_predict": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "gm3d_mask_centers": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp],
-    "gm3d_patch_chamfer_l1_loss_fwd": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
-    "gm3d_patch_chamfer_l1_loss_bwd": [_vp, ctypes.c_longlong, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp],
-    "gm3d_knn_probe_normalize": [_vp, _i, _i, _vp, _vp],
-    "gm3d_knn_probe_neighbours": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp],
-    "gm3d_knn_probe_classify": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp],
-    "gm3d_gemm_tn_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _vp],
-    "gm3d_gemm_nt_f32": [_vp, _vp, _vp, _vp, _i, _i, _i, _i] + [ctypes.c_longlong] * 6 + [_i, _i, _vp],
-    "gm3d_gemm_nt_f32_splits": [_i, _i, _i, _i],
-    "gm3d_gemm_nt_f32_slab_rows": [_i, _i],
-    "gm3d_sample_normalize": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp],
-    "gm3d_augment": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
-    "gm3d_linprobe_slices": [_i],
-    "gm3d_linprobe_train": [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _f] + [_vp] * 9 + [_vp],
-    "gm3d_linprobe_eval": [_vp, _vp, _i, _i, _i] + [_vp] * 7 + [_vp],
-    "gm3d_reconstruct_assemble": [_vp, ctypes.c_longlong, _vp, _vp, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _i, _i, _i, _i, _i,
-                                  _i, _vp, _vp, _i, _vp],
-    "gm3d_reconstruct_partition": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-}
+
+def _ctype(c_type, func, table=_CTYPES):
+    """The ctypes type of one C type as the header spells it (qualifiers and the parameter's name already removed)."""
+    if "*" in c_type:
+        return ctypes.c_void_p
+    if c_type not in table:
+        raise ImportError("gm3d_amd: %s: no ctypes mapping for the type %r in include/gm3d.h" % (func, c_type))
+    return table[c_type]
+
+
+def parse_header(text):
+    """name -> (restype, argtypes) for every function that the header text declares."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    out = {}
+    for ret, name, params in _DECL.findall(text):
+        ret = " ".join(ret.replace("const", " ").split())
+        restype = ctypes.c_char_p if ret == "char *" else _ctype(ret, name, {"int": ctypes.c_int})
+        argtypes = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            words = p.replace("const", " ").replace("*", " * ").split()
+            argtypes.append(_ctype(" ".join(words[:-1]), name))      # the last word is the parameter's name
+        out[name] = (restype, argtypes)
+    return out
+
+
+with open(HEADER) as _f:
+    _PARSED = parse_header(_f.read())
+# name -> argtypes, derived from include/gm3d.h (tests/test_capi_symbols.py pins the parser)
+SIGNATURES = {name: argtypes for name, (_, argtypes) in _PARSED.items()}
 
 
 class Gm3dError(RuntimeError):
@@ -178,10 +59,10 @@ def _load():
             "gm3d_amd: %s not found. Build it with `python -m gm3d_amd.build` "
             "(hipcc, --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in _PARSED.items():
         fn = getattr(lib, name)  # AttributeError = ABI mismatch: fail loudly
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_char_p if name == "gm3d_strerror" else ctypes.c_int
+        fn.restype = restype
     return lib
 
 

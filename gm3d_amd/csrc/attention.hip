@@ -683,15 +683,19 @@ extern "C" int gm3d_attention_fwd(const void* qkv, void* out, float* lse, int B,
     const int nt = (T + 31) / 32;
     if (dtype == GM3D_BF16) {
         const size_t lds = (size_t)3 * 32 * nt * 128;
-#define GM3D_AF(NT_) launch_lds<attn_fwd_bf16_kernel<NT_>>(dim3(B * H), dim3(64 * NT_), lds, stream, (const bf16_t*)qkv, (bf16_t*)out, lse, T, H, scale)
-        return nt == 1 ? GM3D_AF(1) : nt == 2 ? GM3D_AF(2) : nt == 3 ? GM3D_AF(3) : GM3D_AF(4);
-#undef GM3D_AF
+        return by_int<1, 2, 3, 4>(nt, [&](auto c) {
+            constexpr int NT = decltype(c)::value;
+            return launch_lds<attn_fwd_bf16_kernel<NT>>(dim3(B * H), dim3(64 * NT), lds, stream, (const bf16_t*)qkv, (bf16_t*)out, lse, T, H,
+                                                        scale);
+        });
     }
     const int threads = 64 * nt;
     const int rows = T <= 64 ? 64 : 128;
     const size_t lds = sizeof(float) * 3 * rows * 64;
-    return T <= 64 ? launch_lds<attn_fwd_f32_kernel<2>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv, (float*)out, lse, T, H, scale)
-                   : launch_lds<attn_fwd_f32_kernel<4>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv, (float*)out, lse, T, H, scale);
+    return by_int<2, 4>(T <= 64 ? 2 : 4, [&](auto c) {
+        return launch_lds<attn_fwd_f32_kernel<decltype(c)::value>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv, (float*)out,
+                                                                   lse, T, H, scale);
+    });
 }
 
 extern "C" int gm3d_attention_qkv_fwd(const void* h, const void* wqkv, void* out, float* lse, void* qkv_out, int B, int T, int H,
@@ -722,17 +726,17 @@ extern "C" int gm3d_attention_bwd(const void* qkv, const void* out, const void* 
     const int nt = (T + 31) / 32;
     if (dtype == GM3D_BF16) {
         const size_t lds = (size_t)4 * 32 * nt * 128 + 2 * 32 * nt * sizeof(float);
-#define GM3D_AB(NT_)                                                                                                      \
-    launch_lds<attn_bwd_bf16_kernel<NT_>>(dim3(B * H), dim3(128 * NT_), lds, stream, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, \
-                (bf16_t*)dqkv, T, H, scale)
-        return nt == 1 ? GM3D_AB(1) : nt == 2 ? GM3D_AB(2) : nt == 3 ? GM3D_AB(3) : GM3D_AB(4);
-#undef GM3D_AB
+        return by_int<1, 2, 3, 4>(nt, [&](auto c) {
+            constexpr int NT = decltype(c)::value;
+            return launch_lds<attn_bwd_bf16_kernel<NT>>(dim3(B * H), dim3(128 * NT), lds, stream, (const bf16_t*)qkv, (const bf16_t*)out,
+                                                        (const bf16_t*)dout, lse, (bf16_t*)dqkv, T, H, scale);
+        });
     }
     const int threads = 128 * nt;   // NT key-tile waves + NT query-tile waves
     const int rows = T <= 64 ? 64 : 128;
     const size_t lds = sizeof(float) * (4 * rows * 64 + 2 * rows);
-    return T <= 64 ? launch_lds<attn_bwd_f32_kernel<2>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv, (const float*)out,
-                                 (const float*)dout, lse, (float*)dqkv, T, H, scale)
-                   : launch_lds<attn_bwd_f32_kernel<4>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv, (const float*)out,
-                                 (const float*)dout, lse, (float*)dqkv, T, H, scale);
+    return by_int<2, 4>(T <= 64 ? 2 : 4, [&](auto c) {
+        return launch_lds<attn_bwd_f32_kernel<decltype(c)::value>>(dim3(B * H), dim3(threads), lds, stream, (const float*)qkv,
+                                                                   (const float*)out, (const float*)dout, lse, (float*)dqkv, T, H, scale);
+    });
 }

@@ -568,17 +568,17 @@ extern "C" int gm3d_attention_long_fwd(const void* qkv, const unsigned* mask, vo
     if (dtype == GM3D_F32) {
         const size_t lds = (size_t)4 * LCH * (HD + 1) * sizeof(float);
         const dim3 grid(B * H, (T + 255) / 256);
-#define GM3D_LF(HD_)                                                                                                              \
-    launch_lds<lattn_fwd_f32_kernel<HD_>>(grid, dim3(512), lds, stream, (const float*)qkv, mask, (float*)out, lse, T, H, W, scale)
-        return HD == 16 ? GM3D_LF(16) : HD == 32 ? GM3D_LF(32) : GM3D_LF(64);
-#undef GM3D_LF
+        return by_int<16, 32, 64>(HD, [&](auto c) {
+            return launch_lds<lattn_fwd_f32_kernel<decltype(c)::value>>(grid, dim3(512), lds, stream, (const float*)qkv, mask, (float*)out,
+                                                                        lse, T, H, W, scale);
+        });
     }
     const size_t lds = (size_t)(4 * LCH + 256) * (HD * 2 + 16);
     const dim3 grid(B * H, (T + 255) / 256);
-#define GM3D_LF(HD_)                                                                                                              \
-    launch_lds<lattn_fwd_bf16_kernel<HD_>>(grid, dim3(512), lds, stream, (const bf16_t*)qkv, mask, (bf16_t*)out, lse, T, H, W, scale)
-    return HD == 16 ? GM3D_LF(16) : HD == 32 ? GM3D_LF(32) : GM3D_LF(64);
-#undef GM3D_LF
+    return by_int<16, 32, 64>(HD, [&](auto c) {
+        return launch_lds<lattn_fwd_bf16_kernel<decltype(c)::value>>(grid, dim3(512), lds, stream, (const bf16_t*)qkv, mask, (bf16_t*)out,
+                                                                     lse, T, H, W, scale);
+    });
 }
 
 extern "C" int gm3d_attention_long_bwd(const void* qkv, const unsigned* mask, const void* out, const void* dout, const float* lse,
@@ -592,17 +592,17 @@ extern "C" int gm3d_attention_long_bwd(const void* qkv, const unsigned* mask, co
     if (dtype == GM3D_F32) {
         const size_t lds = (size_t)2 * (4 * LCH * (HD + 1) + 2 * LCH) * sizeof(float);
         const dim3 grid(B * H, (T + 127) / 128);
-#define GM3D_LB(HD_)                                                                                                              \
-    launch_lds<lattn_bwd_f32_kernel<HD_>>(grid, dim3(512), lds, stream, (const float*)qkv, mask, (const float*)out, (const float*)dout, \
-                                          lse, (float*)dqkv, T, H, W, scale)
-        return HD == 16 ? GM3D_LB(16) : HD == 32 ? GM3D_LB(32) : GM3D_LB(64);
-#undef GM3D_LB
+        return by_int<16, 32, 64>(HD, [&](auto c) {
+            return launch_lds<lattn_bwd_f32_kernel<decltype(c)::value>>(grid, dim3(512), lds, stream, (const float*)qkv, mask,
+                                                                        (const float*)out, (const float*)dout, lse, (float*)dqkv, T, H, W,
+                                                                        scale);
+        });
     }
     const size_t lds = (size_t)2 * (4 * LCH * (HD * 2 + 16) + 2 * LCH * sizeof(float));
     const dim3 grid(B * H, (T + 127) / 128);       // 4 key tiles (= query tiles) per workgroup
-#define GM3D_LB(HD_)                                                                                                              \
-    launch_lds<lattn_bwd_bf16_kernel<HD_>>(grid, dim3(512), lds, stream, (const bf16_t*)qkv, mask, (const bf16_t*)out,              \
-                                           (const bf16_t*)dout, lse, (bf16_t*)dqkv, T, H, W, scale)
-    return HD == 16 ? GM3D_LB(16) : HD == 32 ? GM3D_LB(32) : GM3D_LB(64);
-#undef GM3D_LB
+    return by_int<16, 32, 64>(HD, [&](auto c) {
+        return launch_lds<lattn_bwd_bf16_kernel<decltype(c)::value>>(grid, dim3(512), lds, stream, (const bf16_t*)qkv, mask,
+                                                                     (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv, T, H, W,
+                                                                     scale);
+    });
 }

@@ -440,7 +440,7 @@ extern "C" int gm3d_radius_mask_bits_m(const float* center, const unsigned char*
     if (B == 0) return GM3D_OK;
     const int W = (G + 31) / 32;
     if (G > 8192 || B > 65535) return GM3D_EUNSUPPORTED;
-    const size_t lds = (size_t)4 * G * sizeof(float);       // G > 4096: above the 64 KiB default, up to 128 KiB at G = 8192
+    const size_t lds = (size_t)4 * G * sizeof(float);       // G > 3072: above the 48 KiB default, up to 128 KiB at G = 8192
     return launch_lds<radius_mask_bits_kernel>(dim3((unsigned)((G * W + 255) / 256), (unsigned)B), dim3(256), lds, stream, center, vis,
                                                radius, B, G, W, bits, inv);
 }
@@ -468,9 +468,10 @@ extern "C" int gm3d_attention_masked_fwd(const void* qkv, const unsigned* mask, 
     }
     const long long n = (long long)B * H * T;
     const dim3 grid((unsigned)((n + 127) / 128));
-#define GM3D_MF(HD_) launch_lds<mattn_fwd_f32_kernel<HD_>>(grid, dim3(128), 0, stream, (const float*)qkv, mask, (float*)out, lse, B, T, H, W, scale)
-    return HD == 16 ? GM3D_MF(16) : HD == 32 ? GM3D_MF(32) : GM3D_MF(64);
-#undef GM3D_MF
+    return by_int<16, 32, 64>(HD, [&](auto c) {
+        return launch_lds<mattn_fwd_f32_kernel<decltype(c)::value>>(grid, dim3(128), 0, stream, (const float*)qkv, mask, (float*)out, lse, B,
+                                                                    T, H, W, scale);
+    });
 }
 
 extern "C" int gm3d_attention_masked_bwd(const void* qkv, const unsigned* mask, const void* out, const void* dout, const float* lse,
@@ -496,9 +497,8 @@ extern "C" int gm3d_attention_masked_bwd(const void* qkv, const unsigned* mask, 
     }
     const long long n = (long long)B * H * T;
     const dim3 grid((unsigned)((n + 127) / 128), 2);
-#define GM3D_MB(HD_)                                                                                                                \
-    launch_lds<mattn_bwd_f32_kernel<HD_>>(grid, dim3(128), 0, stream, (const float*)qkv, mask, (const float*)out, (const float*)dout, lse, \
-                                          (float*)dqkv, B, T, H, W, scale)
-    return HD == 16 ? GM3D_MB(16) : HD == 32 ? GM3D_MB(32) : GM3D_MB(64);
-#undef GM3D_MB
+    return by_int<16, 32, 64>(HD, [&](auto c) {
+        return launch_lds<mattn_bwd_f32_kernel<decltype(c)::value>>(grid, dim3(128), 0, stream, (const float*)qkv, mask, (const float*)out,
+                                                                    (const float*)dout, lse, (float*)dqkv, B, T, H, W, scale);
+    });
 }

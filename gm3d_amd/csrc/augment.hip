@@ -230,7 +230,5 @@ extern "C" int gm3d_augment(float* pc, int B, int N, int nops, const int* ops, c
     if ((D > 0 && !cloud_u) || (dropouts && !point_u) || (jitters && !point_z)) return GM3D_EINVAL;
     if (B == 0) return GM3D_OK;
     const int threads = N >= AUG_THREADS_MAX ? AUG_THREADS_MAX : (N + GM3D_WAVE - 1) / GM3D_WAVE * GM3D_WAVE;
-    hipLaunchKernelGGL(augment_kernel, dim3((unsigned)B), dim3(threads), 0, (hipStream_t)stream, pc, cloud_u, point_u, point_z, B, N, prog);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<augment_kernel>(dim3((unsigned)B), dim3(threads), 0, stream, pc, cloud_u, point_u, point_z, B, N, prog);
 }

@@ -348,27 +348,18 @@ extern "C" int gm3d_chamfer_fwd(const float* xyz1, const float* xyz2, int P, int
     using namespace gm3d;
     if (!xyz1 || !xyz2 || !dist1 || !dist2 || !idx1 || !idx2 || P < 0 || n < 1 || m < 1) return GM3D_EINVAL;
     if (P == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 32 && m == 32) {
-        hipLaunchKernelGGL(chamfer32_fwd_kernel, dim3((P + 3) / 4), dim3(256), 0, st, xyz1, xyz2, P, dist1, dist2,
-                           idx1, idx2);
-        GM3D_CHECK_LAUNCH();
-        return GM3D_OK;
-    }
-    if (n == m && (n == 8 || n == 16)) {
-        if (n == 8) hipLaunchKernelGGL(chamfer_small_fwd_kernel<8>, dim3((P + 31) / 32), dim3(256), 0, st, xyz1, xyz2, P, dist1, dist2, idx1, idx2);
-        else hipLaunchKernelGGL(chamfer_small_fwd_kernel<16>, dim3((P + 15) / 16), dim3(256), 0, st, xyz1, xyz2, P, dist1, dist2, idx1, idx2);
-        GM3D_CHECK_LAUNCH();
-        return GM3D_OK;
-    }
+    if (n == 32 && m == 32)
+        return launch_lds<chamfer32_fwd_kernel>(dim3((P + 3) / 4), dim3(256), 0, stream, xyz1, xyz2, P, dist1, dist2, idx1, idx2);
+    if (n == m && (n == 8 || n == 16))              // 256 / n patches per workgroup
+        return by_int<8, 16>(n, [&](auto c) {
+            constexpr int N = decltype(c)::value, PPB = 256 / N;
+            return launch_lds<chamfer_small_fwd_kernel<N>>(dim3((P + PPB - 1) / PPB), dim3(256), 0, stream, xyz1, xyz2, P, dist1, dist2,
+                                                           idx1, idx2);
+        });
     if (P > 65535) return GM3D_EUNSUPPORTED;
-    hipLaunchKernelGGL(chamfer_fwd_general_kernel, dim3((n + 255) / 256, P), dim3(256), 0, st, xyz1, xyz2, n, m,
-                       dist1, idx1);
-    GM3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(chamfer_fwd_general_kernel, dim3((m + 255) / 256, P), dim3(256), 0, st, xyz2, xyz1, m, n,
-                       dist2, idx2);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    const int rc = launch_lds<chamfer_fwd_general_kernel>(dim3((n + 255) / 256, P), dim3(256), 0, stream, xyz1, xyz2, n, m, dist1, idx1);
+    if (rc != GM3D_OK) return rc;
+    return launch_lds<chamfer_fwd_general_kernel>(dim3((m + 255) / 256, P), dim3(256), 0, stream, xyz2, xyz1, m, n, dist2, idx2);
 }
 
 extern "C" int gm3d_chamfer_bwd(const float* xyz1, const float* xyz2, const int32_t* idx1, const int32_t* idx2,
@@ -377,41 +368,28 @@ extern "C" int gm3d_chamfer_bwd(const float* xyz1, const float* xyz2, const int3
     using namespace gm3d;
     if (!xyz1 || !xyz2 || !idx1 || !idx2 || !gxyz1 || !gxyz2 || P < 0 || n < 1 || m < 1) return GM3D_EINVAL;
     if (P == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (n == 32 && m == 32) {
-        hipLaunchKernelGGL(chamfer32_bwd_kernel, dim3((P + 3) / 4), dim3(256), 0, st, xyz1, xyz2, idx1, idx2,
-                           grad_dist1, grad_dist2, P, gxyz1, gxyz2);
-        GM3D_CHECK_LAUNCH();
-        return GM3D_OK;
-    }
-    if (n == m && (n == 8 || n == 16)) {
-        if (n == 8) hipLaunchKernelGGL(chamfer_small_bwd_kernel<8>, dim3((P + 31) / 32), dim3(256), 0, st, xyz1, xyz2, idx1, idx2, grad_dist1,
-                                       grad_dist2, P, gxyz1, gxyz2);
-        else hipLaunchKernelGGL(chamfer_small_bwd_kernel<16>, dim3((P + 15) / 16), dim3(256), 0, st, xyz1, xyz2, idx1, idx2, grad_dist1,
-                                grad_dist2, P, gxyz1, gxyz2);
-        GM3D_CHECK_LAUNCH();
-        return GM3D_OK;
-    }
+    if (n == 32 && m == 32)
+        return launch_lds<chamfer32_bwd_kernel>(dim3((P + 3) / 4), dim3(256), 0, stream, xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2, P,
+                                                gxyz1, gxyz2);
+    if (n == m && (n == 8 || n == 16))              // 256 / n patches per workgroup
+        return by_int<8, 16>(n, [&](auto c) {
+            constexpr int N = decltype(c)::value, PPB = 256 / N;
+            return launch_lds<chamfer_small_bwd_kernel<N>>(dim3((P + PPB - 1) / PPB), dim3(256), 0, stream, xyz1, xyz2, idx1, idx2,
+                                                           grad_dist1, grad_dist2, P, gxyz1, gxyz2);
+        });
     if (P > 65535) return GM3D_EUNSUPPORTED;
     const size_t na = (size_t)P * n * 3, nb = (size_t)P * m * 3;
-    hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)((na + 255) / 256 < 2048 ? (na + 255) / 256 : 2048)), dim3(256), 0, st, gxyz1, na);
-    hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)((nb + 255) / 256 < 2048 ? (nb + 255) / 256 : 2048)), dim3(256), 0, st, gxyz2, nb);
-    GM3D_CHECK_LAUNCH();
-    if (grad_dist1) {
-        hipLaunchKernelGGL(chamfer_bwd_general_kernel, dim3((n + 255) / 256, P), dim3(256), 0, st, xyz1, xyz2, idx1,
-                           grad_dist1, n, m, gxyz1, gxyz2);
-        GM3D_CHECK_LAUNCH();
-    }
-    if (grad_dist2) {
-        hipLaunchKernelGGL(chamfer_bwd_general_kernel, dim3((m + 255) / 256, P), dim3(256), 0, st, xyz2, xyz1, idx2,
-                           grad_dist2, m, n, gxyz2, gxyz1);
-        GM3D_CHECK_LAUNCH();
-    }
-    return GM3D_OK;
+    int rc = launch_lds<zero_f32_kernel>(dim3((unsigned)((na + 255) / 256 < 2048 ? (na + 255) / 256 : 2048)), dim3(256), 0, stream, gxyz1, na);
+    if (rc == GM3D_OK)
+        rc = launch_lds<zero_f32_kernel>(dim3((unsigned)((nb + 255) / 256 < 2048 ? (nb + 255) / 256 : 2048)), dim3(256), 0, stream, gxyz2, nb);
+    if (rc == GM3D_OK && grad_dist1)
+        rc = launch_lds<chamfer_bwd_general_kernel>(dim3((n + 255) / 256, P), dim3(256), 0, stream, xyz1, xyz2, idx1, grad_dist1, n, m,
+                                                    gxyz1, gxyz2);
+    if (rc == GM3D_OK && grad_dist2)
+        rc = launch_lds<chamfer_bwd_general_kernel>(dim3((m + 255) / 256, P), dim3(256), 0, stream, xyz2, xyz1, idx2, grad_dist2, m, n,
+                                                    gxyz2, gxyz1);
+    return rc;
 }
-
-#define GM3D_CH_DISPATCH(dtype, CALL_BF16, CALL_F32) \
-    do { if ((dtype) == GM3D_BF16) { CALL_BF16; } else { CALL_F32; } } while (0)
 
 extern "C" int gm3d_patch_chamfer_loss_fwd(const void* pred, long long pred_bstride, const float* target, const long long* ids,
                                            long long ids_bstride, int B, int T, int M, float* matrix, int32_t* idx1, int32_t* idx2,
@@ -421,16 +399,14 @@ extern "C" int gm3d_patch_chamfer_loss_fwd(const void* pred, long long pred_bstr
     if (pred_bstride < (long long)M * 96 || ids_bstride < M) return GM3D_EINVAL;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if ((long long)B * M > 0x7ffffff0LL) return GM3D_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
     const int P = B * M;
-    GM3D_CH_DISPATCH(dtype,
-                  hipLaunchKernelGGL(patch_loss_fwd_kernel<bf16_t>, dim3((P + 3) / 4), dim3(256), 0, st, (const bf16_t*)pred,
-                                     (size_t)pred_bstride, target, ids, (size_t)ids_bstride, B, T, M, matrix, idx1, idx2),
-                  hipLaunchKernelGGL(patch_loss_fwd_kernel<float>, dim3((P + 3) / 4), dim3(256), 0, st, (const float*)pred,
-                                     (size_t)pred_bstride, target, ids, (size_t)ids_bstride, B, T, M, matrix, idx1, idx2));
-    hipLaunchKernelGGL(mean_small_kernel, dim3(1), dim3(256), 0, st, matrix, P, mean_out);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    const int rc = by_dtype(dtype, [&](auto* t) {
+        using E = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<patch_loss_fwd_kernel<E>>(dim3((P + 3) / 4), dim3(256), 0, stream, (const E*)pred, (size_t)pred_bstride, target,
+                                                    ids, (size_t)ids_bstride, B, T, M, matrix, idx1, idx2);
+    });
+    if (rc != GM3D_OK) return rc;
+    return launch_lds<mean_small_kernel>(dim3(1), dim3(256), 0, stream, matrix, P, mean_out);
 }
 
 extern "C" int gm3d_patch_chamfer_loss_bwd_full(const void* pred, long long pred_bstride, const float* target, const long long* ids,
@@ -440,15 +416,12 @@ extern "C" int gm3d_patch_chamfer_loss_bwd_full(const void* pred, long long pred
     if (!pred || !target || !ids || !idx1 || !idx2 || !gmean || !dpred || B < 1 || T < 1 || M < 1 || M > T || lead < 0) return GM3D_EINVAL;
     if (pred_bstride < (long long)M * 96 || ids_bstride < M) return GM3D_EINVAL;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     const int P = B * (lead + M);
-    GM3D_CH_DISPATCH(dtype,
-                  hipLaunchKernelGGL(patch_loss_bwd_kernel<bf16_t>, dim3((P + 3) / 4), dim3(256), 0, st, (const bf16_t*)pred,
-                                     (size_t)pred_bstride, target, ids, (size_t)ids_bstride, idx1, idx2, gmean, B, T, M, (bf16_t*)dpred, lead),
-                  hipLaunchKernelGGL(patch_loss_bwd_kernel<float>, dim3((P + 3) / 4), dim3(256), 0, st, (const float*)pred,
-                                     (size_t)pred_bstride, target, ids, (size_t)ids_bstride, idx1, idx2, gmean, B, T, M, (float*)dpred, lead));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using E = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<patch_loss_bwd_kernel<E>>(dim3((P + 3) / 4), dim3(256), 0, stream, (const E*)pred, (size_t)pred_bstride, target,
+                                                    ids, (size_t)ids_bstride, idx1, idx2, gmean, B, T, M, (E*)dpred, lead);
+    });
 }
 
 extern "C" int gm3d_patch_chamfer_loss_bwd(const void* pred, long long pred_bstride, const float* target, const long long* ids,
@@ -466,18 +439,14 @@ extern "C" int gm3d_patch_chamfer_l1_loss_fwd(const void* pred, long long pred_b
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if ((long long)B * M > 0x3ffffffLL) return GM3D_EUNSUPPORTED;      // B * M * 32 is formed in int
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const int P = B * M;
-    const auto kb = patch_loss_fwd_kernel<bf16_t, true>;
-    const auto kf = patch_loss_fwd_kernel<float, true>;
-    GM3D_CH_DISPATCH(dtype,
-                  hipLaunchKernelGGL(kb, dim3((P + 3) / 4), dim3(256), 0, st, (const bf16_t*)pred, (size_t)pred_bstride, target, ids,
-                                     (size_t)ids_bstride, B, T, M, matrix, idx1, idx2),
-                  hipLaunchKernelGGL(kf, dim3((P + 3) / 4), dim3(256), 0, st, (const float*)pred, (size_t)pred_bstride, target, ids,
-                                     (size_t)ids_bstride, B, T, M, matrix, idx1, idx2));
-    hipLaunchKernelGGL(mean_small_kernel, dim3(1), dim3(256), 0, st, matrix, P, mean_out);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    const int rc = by_dtype(dtype, [&](auto* t) {
+        using E = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<patch_loss_fwd_kernel<E, true>>(dim3((P + 3) / 4), dim3(256), 0, stream, (const E*)pred, (size_t)pred_bstride,
+                                                          target, ids, (size_t)ids_bstride, B, T, M, matrix, idx1, idx2);
+    });
+    if (rc != GM3D_OK) return rc;
+    return launch_lds<mean_small_kernel>(dim3(1), dim3(256), 0, stream, matrix, P, mean_out);
 }
 
 extern "C" int gm3d_patch_chamfer_l1_loss_bwd(const void* pred, long long pred_bstride, const float* target, const long long* ids,
@@ -489,15 +458,10 @@ extern "C" int gm3d_patch_chamfer_l1_loss_bwd(const void* pred, long long pred_b
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if ((long long)B * M > 0x3ffffffLL) return GM3D_EUNSUPPORTED;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const int P = B * M;
-    const auto kb = patch_loss_bwd_kernel<bf16_t, true>;
-    const auto kf = patch_loss_bwd_kernel<float, true>;
-    GM3D_CH_DISPATCH(dtype,
-                  hipLaunchKernelGGL(kb, dim3((P + 3) / 4), dim3(256), 0, st, (const bf16_t*)pred, (size_t)pred_bstride, target, ids,
-                                     (size_t)ids_bstride, idx1, idx2, gmean, B, T, M, (bf16_t*)dpred, 0),
-                  hipLaunchKernelGGL(kf, dim3((P + 3) / 4), dim3(256), 0, st, (const float*)pred, (size_t)pred_bstride, target, ids,
-                                     (size_t)ids_bstride, idx1, idx2, gmean, B, T, M, (float*)dpred, 0));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using E = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<patch_loss_bwd_kernel<E, true>>(dim3((P + 3) / 4), dim3(256), 0, stream, (const E*)pred, (size_t)pred_bstride,
+                                                          target, ids, (size_t)ids_bstride, idx1, idx2, gmean, B, T, M, (E*)dpred, 0);
+    });
 }

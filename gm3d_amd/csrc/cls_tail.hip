@@ -386,11 +386,10 @@ extern "C" int gm3d_cls_tail_fwd(const void* x, int B, int T, int C, int mode, c
         return GM3D_EINVAL;
     if (training && (B < 2 || !nbt1 || !nbt2)) return GM3D_EINVAL;         // batch statistics need two rows
     if (!aligned16(W2) || !aligned16(W3)) return GM3D_EUNSUPPORTED;          // 16-byte weight-row loads
-    int r;
-    if (dtype == GM3D_BF16)
-        r = launch_lds<cls_pool_l1_kernel<bf16_t>>(dim3(B), dim3(POOL_THREADS), 0, stream, (const bf16_t*)x, T, mode, W1, b1, feat, argmax, h);
-    else
-        r = launch_lds<cls_pool_l1_kernel<float>>(dim3(B), dim3(POOL_THREADS), 0, stream, (const float*)x, T, mode, W1, b1, feat, argmax, h);
+    const int r = by_dtype(dtype, [&](auto* t) {
+        using E = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<cls_pool_l1_kernel<E>>(dim3(B), dim3(POOL_THREADS), 0, stream, (const E*)x, T, mode, W1, b1, feat, argmax, h);
+    });
     if (r != GM3D_OK) return r;
     const HeadFwd a{W2, b2, W3, b3, BnArgs{g1, be1, rm1, rv1, nbt1}, BnArgs{g2, be2, rm2, rv2, nbt2}, drop, labels, h, stats, logits, loss};
     const size_t lds = ((size_t)B * CT_H + B) * sizeof(float);
@@ -415,9 +414,9 @@ extern "C" int gm3d_cls_tail_bwd(int B, int T, int C, int mode, const float* W1,
     if (r != GM3D_OK) return r;
     const int F = mode ? 2 * CT_C : CT_C;
     const dim3 grid(B + F + CT_H + cls_dim);
-    if (dtype == GM3D_BF16)
-        return launch_lds<cls_pool_bwd_kernel<bf16_t>>(grid, dim3(POOL_THREADS), 0, stream, B, T, mode, cls_dim, W1, feat, argmax,
-                                                       (const float*)ws, (bf16_t*)dx, dW1, dW2, db2, dW3, db3);
-    return launch_lds<cls_pool_bwd_kernel<float>>(grid, dim3(POOL_THREADS), 0, stream, B, T, mode, cls_dim, W1, feat, argmax,
-                                                  (const float*)ws, (float*)dx, dW1, dW2, db2, dW3, db3);
+    return by_dtype(dtype, [&](auto* t) {
+        using E = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<cls_pool_bwd_kernel<E>>(grid, dim3(POOL_THREADS), 0, stream, B, T, mode, cls_dim, W1, feat, argmax,
+                                                  (const float*)ws, (E*)dx, dW1, dW2, db2, dW3, db3);
+    });
 }

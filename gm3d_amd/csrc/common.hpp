@@ -3,17 +3,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <type_traits>
 #include "../../include/gm3d.h"
 
 #define GM3D_WAVE 64
 
-#define GM3D_CHECK_LAUNCH()                                   \
-    do {                                                      \
-        hipError_t e__ = hipGetLastError();                   \
-        if (e__ != hipSuccess) return GM3D_ELAUNCH;           \
-    } while (0)
-
 namespace gm3d {
+
+typedef __bf16 bf16_t;
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel: lds_grant<Kernel> remembers, per device
 // ordinal, how many bytes were granted (a process that launches on a second device, or two threads racing through the first
@@ -34,15 +31,26 @@ template <auto Kernel> LdsGrant lds_grant;      // one per kernel (keyed on the 
 
 constexpr size_t GM3D_LDS_DEFAULT = 48 * 1024, GM3D_LDS_MAX = 160 * 1024;
 
-// Launches Kernel<<<grid, block, lds, stream>>>(args...) and checks the launch.  More than the CU's 160 KiB of LDS is refused before
-// any HIP call (GM3D_EUNSUPPORTED); above 48 KiB the kernel's per-device LDS limit is raised first (once per kernel and device).
+// The one place that launches a kernel and reads the launch status: Kernel<<<grid, block, lds, stream>>>(args...).  More than the
+// CU's 160 KiB of LDS is refused before any HIP call (GM3D_EUNSUPPORTED); above 48 KiB the kernel's per-device LDS limit is raised
+// first (once per kernel and device).  An entry point that launches more than once returns the first status that is not GM3D_OK.
 template <auto Kernel, class... Args>
 int launch_lds(dim3 grid, dim3 block, size_t lds, gm3d_stream_t stream, Args... args) {
     if (lds > GM3D_LDS_MAX) return GM3D_EUNSUPPORTED;
     if (lds > GM3D_LDS_DEFAULT && !lds_grant<Kernel>.ensure((const void*)Kernel, lds)) return GM3D_ELAUNCH;
     hipLaunchKernelGGL(Kernel, grid, block, lds, (hipStream_t)stream, args...);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return hipGetLastError() == hipSuccess ? GM3D_OK : GM3D_ELAUNCH;
+}
+
+// Calls f with a null `bf16_t*` or `float*` for a dtype that the entry point has already validated, so that a launch over the two
+// element types is written once: inside f, `using T = std::remove_pointer_t<decltype(t)>;` names the element type.
+template <class F> int by_dtype(int dtype, F&& f) { return dtype == GM3D_BF16 ? f((bf16_t*)nullptr) : f((float*)nullptr); }
+
+// The same for a small set of integer template arguments: calls f(std::integral_constant<int, N>) for the first N of the list
+// that equals n, and for the last of the list when none does; inside f, `decltype(c)::value` is the constant.
+template <int N, int... Rest, class F> int by_int(int n, F&& f) {
+    if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, N>{});
+    else return n == N ? f(std::integral_constant<int, N>{}) : by_int<Rest...>(n, f);
 }
 
 // Squared distance with the evaluation order fixed by the oracle contract
@@ -90,8 +98,6 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
 }
 
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-typedef __bf16 bf16_t;
 
 // 8 consecutive elements of `T` as floats: one 16-byte access in bf16, two in f32.
 template <class T> struct V8;

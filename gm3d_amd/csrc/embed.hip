@@ -927,15 +927,12 @@ static inline int group_grid(int G) { return G < 1024 ? G : 1024; }
 static inline int row_grid(int R, int C) { const int sl = slices_for(C); int g = (R + sl - 1) / sl; return g < 1 ? 1 : (g > 1024 ? 1024 : g); }
 static inline int moments_grid(int R) { int g = (R + 255) / 256; return g < 1 ? 1 : (g > 256 ? 256 : g); }
 // fp64 row-slice reductions: sl slices of C / 8 threads, an LDS tile of sl * q * C doubles (q = 5 for pn_layer1_bwd_stats, 4 for
-// lin3_gelu_bwd) kept within the 64 KiB a launch gets without hipFuncSetAttribute
+// lin3_gelu_bwd) of at most 64 KiB; above 48 KiB launch_lds raises the kernel's dynamic-LDS limit first (once per device)
 static inline int pn1_slices(int C1) { return C1 > 200 ? 4 : 8; }     // C1 = 256: 4 * 5 * 256 * 8 B = 40 KiB (8 slices: 80 KiB)
 static inline int lin3_slices(int C) { return C > 256 ? 4 : 8; }      // C = 256 and C = 512: exactly 64 KiB
 static inline int slice_grid(int R, int sl) { int g = (R + sl - 1) / sl; return g > 1024 ? 1024 : (g < 1 ? 1 : g); }
 
 }  // namespace gm3d
-
-#define GM3D_DISPATCH(dtype, CALL_BF16, CALL_F32) \
-    do { if ((dtype) == GM3D_BF16) { CALL_BF16; } else { CALL_F32; } } while (0)
 
 extern "C" int gm3d_embed_partial_rows(int kind, int n, int C) {
     using namespace gm3d;
@@ -949,9 +946,7 @@ extern "C" int gm3d_embed_partial_rows(int kind, int n, int C) {
 extern "C" int gm3d_moments3(const float* x, int R, double* partial, gm3d_stream_t stream) {
     using namespace gm3d;
     if (!x || !partial || R < 1) return GM3D_EINVAL;
-    hipLaunchKernelGGL(moments3_kernel, dim3(moments_grid(R)), dim3(256), 0, (hipStream_t)stream, x, R, partial);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<moments3_kernel>(dim3(moments_grid(R)), dim3(256), 0, stream, x, R, partial);
 }
 
 extern "C" int gm3d_pn_layer1_fwd(const float* x, const float* wf, const float* bf, void* a1, int R, int C1, int dtype,
@@ -962,12 +957,10 @@ extern "C" int gm3d_pn_layer1_fwd(const float* x, const float* wf, const float* 
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     const size_t total = (size_t)R * (C1 / 8);
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(pn_layer1_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, x, wf, bf, (bf16_t*)a1, R, C1),
-                  hipLaunchKernelGGL(pn_layer1_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, x, wf, bf, (float*)a1, R, C1));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<pn_layer1_fwd_kernel<T>>(dim3(grid), dim3(256), 0, stream, x, wf, bf, (T*)a1, R, C1);
+    });
 }
 
 static int gkc_check(const void* a, const void* b, int G, int K, int C, int dtype) {
@@ -985,14 +978,11 @@ extern "C" int gm3d_group_max_fwd(const void* in, const float* bias, void* out, 
     if (!arg) return GM3D_EINVAL;
     const int gpb = 256 / (C / 8) < 1 ? 1 : 256 / (C / 8);
     int grid = (G + gpb - 1) / gpb; grid = grid > 8192 ? 8192 : grid;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(group_max_fwd_kernel<bf16_t>, dim3(grid), dim3(gpb * (C / 8)), 0, st,
-                                     (const bf16_t*)in, bias, (bf16_t*)out, arg, G, K, C),
-                  hipLaunchKernelGGL(group_max_fwd_kernel<float>, dim3(grid), dim3(gpb * (C / 8)), 0, st,
-                                     (const float*)in, bias, (float*)out, arg, G, K, C));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<group_max_fwd_kernel<T>>(dim3(grid), dim3(gpb * (C / 8)), 0, stream,
+                                                   (const T*)in, bias, (T*)out, arg, G, K, C);
+    });
 }
 
 extern "C" int gm3d_group_max_bwd(const void* dout, const uint8_t* arg, void* din, int G, int K, int C, int dtype,
@@ -1001,14 +991,11 @@ extern "C" int gm3d_group_max_bwd(const void* dout, const uint8_t* arg, void* di
     int rc = gkc_check(dout, din, G, K, C, dtype);
     if (rc != GM3D_OK) return rc;
     if (!arg) return GM3D_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(group_max_bwd_kernel<bf16_t>, dim3(group_grid(G)), dim3(threads_for(C)), 0, st,
-                                     (const bf16_t*)dout, arg, (bf16_t*)din, G, K, C),
-                  hipLaunchKernelGGL(group_max_bwd_kernel<float>, dim3(group_grid(G)), dim3(threads_for(C)), 0, st,
-                                     (const float*)dout, arg, (float*)din, G, K, C));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<group_max_bwd_kernel<T>>(dim3(group_grid(G)), dim3(threads_for(C)), 0, stream,
+                                                   (const T*)dout, arg, (T*)din, G, K, C);
+    });
 }
 
 extern "C" int gm3d_bn_bcast_stats(const void* y0, const void* t, int G, int K, int C, float* partial, int dtype,
@@ -1018,14 +1005,11 @@ extern "C" int gm3d_bn_bcast_stats(const void* y0, const void* t, int G, int K, 
     if (rc != GM3D_OK) return rc;
     if (!partial) return GM3D_EINVAL;
     const size_t lds = (size_t)slices_for(C) * 2 * C * 4;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(bn_bcast_stats_kernel<bf16_t>, dim3(group_grid(G)), dim3(threads_for(C)), lds, st,
-                                     (const bf16_t*)y0, (const bf16_t*)t, G, K, C, partial),
-                  hipLaunchKernelGGL(bn_bcast_stats_kernel<float>, dim3(group_grid(G)), dim3(threads_for(C)), lds, st,
-                                     (const float*)y0, (const float*)t, G, K, C, partial));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* e) {
+        using T = std::remove_pointer_t<decltype(e)>;
+        return launch_lds<bn_bcast_stats_kernel<T>>(dim3(group_grid(G)), dim3(threads_for(C)), lds, stream,
+                                                    (const T*)y0, (const T*)t, G, K, C, partial);
+    });
 }
 
 extern "C" int gm3d_bn_bcast_apply_relu_sel(const void* y0, const void* t, const float* scale, const float* shift, void* a2,
@@ -1034,14 +1018,11 @@ extern "C" int gm3d_bn_bcast_apply_relu_sel(const void* y0, const void* t, const
     int rc = gkc_check(y0, t, G, K, C, dtype);
     if (rc != GM3D_OK) return rc;
     if (!scale || !shift || !a2) return GM3D_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(bn_bcast_apply_relu_kernel<bf16_t>, dim3(group_grid(G)), dim3(threads_for(C)), 0, st,
-                                     (const bf16_t*)y0, (const bf16_t*)t, scale, shift, (bf16_t*)a2, G, K, C, slope, sel),
-                  hipLaunchKernelGGL(bn_bcast_apply_relu_kernel<float>, dim3(group_grid(G)), dim3(threads_for(C)), 0, st,
-                                     (const float*)y0, (const float*)t, scale, shift, (float*)a2, G, K, C, slope, sel));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* e) {
+        using T = std::remove_pointer_t<decltype(e)>;
+        return launch_lds<bn_bcast_apply_relu_kernel<T>>(dim3(group_grid(G)), dim3(threads_for(C)), 0, stream,
+                                                         (const T*)y0, (const T*)t, scale, shift, (T*)a2, G, K, C, slope, sel);
+    });
 }
 
 extern "C" int gm3d_bn_bcast_apply_relu(const void* y0, const void* t, const float* scale, const float* shift, void* a2,
@@ -1057,14 +1038,11 @@ extern "C" int gm3d_bn_bcast_bwd_stats_sel(const void* da2, const void* y0, cons
     if (rc != GM3D_OK) return rc;
     if (!da2 || !scale || !shift || !mean || !rstd || !partial) return GM3D_EINVAL;
     const size_t lds = (size_t)slices_for(C) * 2 * C * 4;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(bn_bcast_bwd_stats_kernel<bf16_t>, dim3(group_grid(G)), dim3(threads_for(C)), lds, st,
-                                     (const bf16_t*)da2, (const bf16_t*)y0, (const bf16_t*)t, scale, shift, mean, rstd, G, K, C, partial, slope, sel),
-                  hipLaunchKernelGGL(bn_bcast_bwd_stats_kernel<float>, dim3(group_grid(G)), dim3(threads_for(C)), lds, st,
-                                     (const float*)da2, (const float*)y0, (const float*)t, scale, shift, mean, rstd, G, K, C, partial, slope, sel));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* e) {
+        using T = std::remove_pointer_t<decltype(e)>;
+        return launch_lds<bn_bcast_bwd_stats_kernel<T>>(dim3(group_grid(G)), dim3(threads_for(C)), lds, stream, (const T*)da2,
+                                                        (const T*)y0, (const T*)t, scale, shift, mean, rstd, G, K, C, partial, slope, sel);
+    });
 }
 
 extern "C" int gm3d_bn_bcast_bwd_stats(const void* da2, const void* y0, const void* t, const float* scale,
@@ -1084,16 +1062,12 @@ extern "C" int gm3d_bn_bcast_bwd_apply_sel(const void* da2, const void* y0, cons
     const float inv_rows = 1.0f / ((float)G * (float)K);
     const int gpb = 256 / (C / 8) < 1 ? 1 : 256 / (C / 8);
     int grid = (G + gpb - 1) / gpb; grid = grid > 8192 ? 8192 : grid;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(bn_bcast_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(gpb * (C / 8)), 0, st,
-                                     (const bf16_t*)da2, (const bf16_t*)y0, (const bf16_t*)t, scale, shift, mean, rstd, s1, s2,
-                                     inv_rows, (bf16_t*)dy, dt, G, K, C, slope, inv),
-                  hipLaunchKernelGGL(bn_bcast_bwd_apply_kernel<float>, dim3(grid), dim3(gpb * (C / 8)), 0, st,
-                                     (const float*)da2, (const float*)y0, (const float*)t, scale, shift, mean, rstd, s1, s2,
-                                     inv_rows, (float*)dy, dt, G, K, C, slope, inv));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* e) {
+        using T = std::remove_pointer_t<decltype(e)>;
+        return launch_lds<bn_bcast_bwd_apply_kernel<T>>(dim3(grid), dim3(gpb * (C / 8)), 0, stream,
+                                                        (const T*)da2, (const T*)y0, (const T*)t, scale, shift, mean, rstd, s1, s2,
+                                                        inv_rows, (T*)dy, dt, G, K, C, slope, inv);
+    });
 }
 
 extern "C" int gm3d_bn_bcast_bwd_apply(const void* da2, const void* y0, const void* t, const float* scale,
@@ -1108,13 +1082,11 @@ extern "C" int gm3d_head_fold(const float* W1, const float* b1, int nout, int C,
     using namespace gm3d;
     if (!W1 || !b1 || !wv || !wv_t || !bm || nout < 1 || C < 1) return GM3D_EINVAL;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     const int grid = (C + 15) / 16 + 1;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(head_fold_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, W1, b1, nout, C, wv, (bf16_t*)wv_t, bm),
-                  hipLaunchKernelGGL(head_fold_kernel<float>, dim3(grid), dim3(256), 0, st, W1, b1, nout, C, wv, (float*)wv_t, bm));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<head_fold_kernel<T>>(dim3(grid), dim3(256), 0, stream, W1, b1, nout, C, wv, (T*)wv_t, bm);
+    });
 }
 
 extern "C" int gm3d_head_rowdot(const void* a, const void* wv_t, const float* bm, int R, int C, float* out, int dtype,
@@ -1124,13 +1096,11 @@ extern "C" int gm3d_head_rowdot(const void* a, const void* wv_t, const float* bm
     if (C < 8 || C % 8) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if (R == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     int grid = (R + 3) / 4; grid = grid > 4096 ? 4096 : grid;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(head_rowdot_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)wv_t, bm, R, C, out),
-                  hipLaunchKernelGGL(head_rowdot_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)a, (const float*)wv_t, bm, R, C, out));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<head_rowdot_kernel<T>>(dim3(grid), dim3(256), 0, stream, (const T*)a, (const T*)wv_t, bm, R, C, out);
+    });
 }
 
 extern "C" int gm3d_head_fold_bwd(const float* dwv, const float* d, int R, int nout, int C, float* dW1, float* db1,
@@ -1139,10 +1109,7 @@ extern "C" int gm3d_head_fold_bwd(const float* dwv, const float* d, int R, int n
     if (!dwv || !d || !dW1 || !db1 || R < 1 || nout < 1 || C < 1) return GM3D_EINVAL;
     long long ew = ((long long)nout * C + 255) / 256;
     const int ew_blocks = (int)(ew > 2048 ? 2048 : ew);
-    hipLaunchKernelGGL(head_fold_bwd_kernel, dim3(ew_blocks + 1), dim3(256), 0, (hipStream_t)stream, dwv, d, R, nout, C, ew_blocks, dW1,
-                       db1);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<head_fold_bwd_kernel>(dim3(ew_blocks + 1), dim3(256), 0, stream, dwv, d, R, nout, C, ew_blocks, dW1, db1);
 }
 
 extern "C" int gm3d_head_outer(const float* d, const float* wv, int R, int C, void* da, int dtype, gm3d_stream_t stream) {
@@ -1151,14 +1118,12 @@ extern "C" int gm3d_head_outer(const float* d, const float* wv, int R, int C, vo
     if (C < 8 || C % 8) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if (R == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const size_t total = (size_t)R * (C / 8);
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(head_outer_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, d, wv, R, C, (bf16_t*)da),
-                  hipLaunchKernelGGL(head_outer_kernel<float>, dim3(grid), dim3(256), 0, st, d, wv, R, C, (float*)da));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<head_outer_kernel<T>>(dim3(grid), dim3(256), 0, stream, d, wv, R, C, (T*)da);
+    });
 }
 
 extern "C" int gm3d_scale_translate(float* pc, const float* u, float lo, float span, float t, int B, int N, gm3d_stream_t stream) {
@@ -1167,10 +1132,7 @@ extern "C" int gm3d_scale_translate(float* pc, const float* u, float lo, float s
     const long long total = (long long)B * N * 3;
     if (total == 0) return GM3D_OK;
     long long grid = (total + 255) / 256;
-    hipLaunchKernelGGL(scale_translate_kernel, dim3((unsigned)(grid > 2048 ? 2048 : grid)), dim3(256), 0, (hipStream_t)stream, pc, u, lo, span,
-                       t, B, N);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<scale_translate_kernel>(dim3((unsigned)(grid > 2048 ? 2048 : grid)), dim3(256), 0, stream, pc, u, lo, span, t, B, N);
 }
 
 extern "C" int gm3d_group_select_maps(const long long* ids, int id_pitch, int B, int V, int G, int* sel, int* inv,
@@ -1179,9 +1141,7 @@ extern "C" int gm3d_group_select_maps(const long long* ids, int id_pitch, int B,
     if (!ids || !sel || !inv || B < 0 || V < 0 || G < 1 || V > G || id_pitch < V) return GM3D_EINVAL;
     if ((long long)B * G > 0x7fffffffLL) return GM3D_EUNSUPPORTED;
     if (B == 0) return GM3D_OK;
-    hipLaunchKernelGGL(group_select_maps_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, ids, id_pitch, V, G, sel, inv);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<group_select_maps_kernel>(dim3(B), dim3(256), 0, stream, ids, id_pitch, V, G, sel, inv);
 }
 
 extern "C" int gm3d_group_scatter_add(void* df, const void* dfg, const uint8_t* arg, int G, int K, int C, float* partial,
@@ -1191,14 +1151,11 @@ extern "C" int gm3d_group_scatter_add(void* df, const void* dfg, const uint8_t* 
     if (rc != GM3D_OK) return rc;
     if (!arg || !partial) return GM3D_EINVAL;
     const size_t lds = (size_t)slices_for(C) * C * 4;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(group_scatter_add_kernel<bf16_t>, dim3(group_grid(G)), dim3(threads_for(C)), lds, st,
-                                     (bf16_t*)df, (const bf16_t*)dfg, arg, G, K, C, partial),
-                  hipLaunchKernelGGL(group_scatter_add_kernel<float>, dim3(group_grid(G)), dim3(threads_for(C)), lds, st,
-                                     (float*)df, (const float*)dfg, arg, G, K, C, partial));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<group_scatter_add_kernel<T>>(dim3(group_grid(G)), dim3(threads_for(C)), lds, stream,
+                                                       (T*)df, (const T*)dfg, arg, G, K, C, partial);
+    });
 }
 
 extern "C" int gm3d_pn_layer1_bwd_stats(const void* da1, const void* a1, const float* x, const float* w1, const float* b1,
@@ -1211,33 +1168,26 @@ extern "C" int gm3d_pn_layer1_bwd_stats(const void* da1, const void* a1, const f
     const int tpr = C1 / 8, sl = pn1_slices(C1);          // fp64 LDS tile at most 64 KiB (C1 <= 200: 8 slices, else 4)
     const size_t lds = (size_t)sl * 5 * C1 * sizeof(double);
     const int grid = slice_grid(R, sl);
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(pn_layer1_bwd_stats_kernel<bf16_t>, dim3(grid), dim3(sl * tpr), lds, st,
-                                     (const bf16_t*)da1, (const bf16_t*)a1, x, w1, b1, mean, rstd, xmean, R, C1, partial),
-                  hipLaunchKernelGGL(pn_layer1_bwd_stats_kernel<float>, dim3(grid), dim3(sl * tpr), lds, st,
-                                     (const float*)da1, (const float*)a1, x, w1, b1, mean, rstd, xmean, R, C1, partial));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<pn_layer1_bwd_stats_kernel<T>>(dim3(grid), dim3(sl * tpr), lds, stream,
+                                                         (const T*)da1, (const T*)a1, x, w1, b1, mean, rstd, xmean, R, C1, partial);
+    });
 }
 
 extern "C" int gm3d_colsum_finish_f64(const double* partial, int nrows, int pitch, int ncols, double* out,
                                       gm3d_stream_t stream) {
     using namespace gm3d;
     if (!partial || !out || nrows < 0 || ncols < 1 || pitch < ncols) return GM3D_EINVAL;
-    hipLaunchKernelGGL(colsum_finish_f64_kernel<false>, dim3((ncols + 31) / 32), dim3(256), 0, (hipStream_t)stream, partial, nrows,
-                       pitch, ncols, out, nullptr, nullptr, 1);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<colsum_finish_f64_kernel<false>>(dim3((ncols + 31) / 32), dim3(256), 0, stream, partial, nrows, pitch, ncols, out,
+                                                       nullptr, nullptr, 1);
 }
 
 extern "C" int gm3d_lin3_finish(const double* partial, int nrows, int C, float* dW, float* db, gm3d_stream_t stream) {
     using namespace gm3d;
     if (!partial || !dW || !db || nrows < 0 || C < 1) return GM3D_EINVAL;
-    hipLaunchKernelGGL(colsum_finish_f64_kernel<true>, dim3((4 * C + 31) / 32), dim3(256), 0, (hipStream_t)stream, partial, nrows, 4 * C,
-                       4 * C, nullptr, dW, db, C);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<colsum_finish_f64_kernel<true>>(dim3((4 * C + 31) / 32), dim3(256), 0, stream, partial, nrows, 4 * C, 4 * C,
+                                                      nullptr, dW, db, C);
 }
 
 extern "C" int gm3d_colsum_partial_w(const void* m, const float* roww, int R, int C, float* partial, int dtype, gm3d_stream_t stream);
@@ -1251,14 +1201,11 @@ extern "C" int gm3d_colsum_partial_w(const void* m, const float* roww, int R, in
     if (C < 8 || C % 8 || C > 2048) return GM3D_EUNSUPPORTED;          // one thread per 8 columns, at most 256 threads per row slice
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     const size_t lds = (size_t)slices_for(C) * C * 4;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(colsum_partial_kernel<bf16_t>, dim3(row_grid(R, C)), dim3(threads_for(C)), lds, st,
-                                     (const bf16_t*)m, R, C, partial, roww),
-                  hipLaunchKernelGGL(colsum_partial_kernel<float>, dim3(row_grid(R, C)), dim3(threads_for(C)), lds, st,
-                                     (const float*)m, R, C, partial, roww));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<colsum_partial_kernel<T>>(dim3(row_grid(R, C)), dim3(threads_for(C)), lds, stream,
+                                                    (const T*)m, R, C, partial, roww);
+    });
 }
 
 extern "C" int gm3d_lin3_gelu_fwd(const float* x, const float* w, const float* b, void* out, int R, int C, int dtype,
@@ -1269,12 +1216,10 @@ extern "C" int gm3d_lin3_gelu_fwd(const float* x, const float* w, const float* b
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     const size_t total = (size_t)R * (C / 8);
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(lin3_gelu_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, x, w, b, (bf16_t*)out, R, C),
-                  hipLaunchKernelGGL(lin3_gelu_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, x, w, b, (float*)out, R, C));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<lin3_gelu_fwd_kernel<T>>(dim3(grid), dim3(256), 0, stream, x, w, b, (T*)out, R, C);
+    });
 }
 
 extern "C" int gm3d_lin3_gelu_bwd(const void* dout, const float* x, const float* w, const float* b, int R, int C,
@@ -1286,12 +1231,10 @@ extern "C" int gm3d_lin3_gelu_bwd(const void* dout, const float* x, const float*
     const int tpr = C / 8, sl = lin3_slices(C);        // C = 384: 192 threads, 48 KiB of fp64 partials
     const size_t lds = (size_t)sl * 4 * C * sizeof(double);
     const int grid = slice_grid(R, sl);
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(lin3_gelu_bwd_kernel<bf16_t>, dim3(grid), dim3(sl * tpr), lds, st, (const bf16_t*)dout, x, w, b, R, C, partial),
-                  hipLaunchKernelGGL(lin3_gelu_bwd_kernel<float>, dim3(grid), dim3(sl * tpr), lds, st, (const float*)dout, x, w, b, R, C, partial));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<lin3_gelu_bwd_kernel<T>>(dim3(grid), dim3(sl * tpr), lds, stream, (const T*)dout, x, w, b, R, C, partial);
+    });
 }
 
 extern "C" int gm3d_rank_loss(const float* pred, const float* target, int B, int M, float* out, float* dpred,
@@ -1300,9 +1243,7 @@ extern "C" int gm3d_rank_loss(const float* pred, const float* target, int B, int
     if (!pred || !target || !out || !dpred || B < 1 || M < 1) return GM3D_EINVAL;
     if (M > GUIDED_MAX) return GM3D_EUNSUPPORTED;
     if (M > GUIDED_NARROW) return launch_rank_loss_wide(pred, M, target, B, M, out, dpred, stream);      // guided.hip: one workgroup per cloud
-    hipLaunchKernelGGL(rank_loss_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pred, M, target, M, out, dpred);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<rank_loss_kernel>(dim3(B), dim3(64), 0, stream, pred, M, target, M, out, dpred);
 }
 
 extern "C" int gm3d_rank_loss_tail(const float* pred, int ldp, const float* target, int B, int M, float* out, float* dpred, float* tot,
@@ -1310,42 +1251,30 @@ extern "C" int gm3d_rank_loss_tail(const float* pred, int ldp, const float* targ
     using namespace gm3d;
     if (!pred || !target || !out || !dpred || !tot || !loss || B < 1 || M < 1 || ldp < M) return GM3D_EINVAL;
     if (M > GUIDED_MAX) return GM3D_EUNSUPPORTED;
-    if (M > GUIDED_NARROW) {
-        const int rc = launch_rank_loss_wide(pred, ldp, target, B, M, out, dpred, stream);
-        if (rc != GM3D_OK) return rc;
-    } else {
-        hipLaunchKernelGGL(rank_loss_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pred, ldp, target, M, out, dpred);
-        GM3D_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(rank_loss_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)out, B, tot, loss);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    const int rc = M > GUIDED_NARROW ? launch_rank_loss_wide(pred, ldp, target, B, M, out, dpred, stream)
+                                     : launch_lds<rank_loss_kernel>(dim3(B), dim3(64), 0, stream, pred, ldp, target, M, out, dpred);
+    if (rc != GM3D_OK) return rc;
+    return launch_lds<rank_loss_finish_kernel>(dim3(1), dim3(256), 0, stream, (const float*)out, B, tot, loss);
 }
 
 extern "C" int gm3d_rank_loss_tail_bwd(const float* dpred, const float* g, const float* tot, int B, int M, int L, float* dfull,
                                        gm3d_stream_t stream) {
     using namespace gm3d;
     if (!dpred || !g || !tot || !dfull || B < 1 || M < 1 || L < M) return GM3D_EINVAL;
-    hipLaunchKernelGGL(rank_loss_bwd_kernel, dim3((B * L + 255) / 256), dim3(256), 0, (hipStream_t)stream, dpred, g, tot, B, M, L, dfull);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<rank_loss_bwd_kernel>(dim3((B * L + 255) / 256), dim3(256), 0, stream, dpred, g, tot, B, M, L, dfull);
 }
 
 extern "C" int gm3d_ema_counters(long long* e, const long long* m, int n, float decay, float w, gm3d_stream_t stream) {
     using namespace gm3d;
     if (!e || !m || n < 0) return GM3D_EINVAL;
     if (n == 0) return GM3D_OK;
-    hipLaunchKernelGGL(ema_counters_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, m, n, decay, w);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<ema_counters_kernel>(dim3((n + 63) / 64), dim3(64), 0, stream, e, m, n, decay, w);
 }
 
 extern "C" int gm3d_drop_path_scales(const float* u, const float* keep, int S, int B, float* out, gm3d_stream_t stream) {
     using namespace gm3d;
     if (!u || !keep || !out || S < 1 || B < 1) return GM3D_EINVAL;
-    hipLaunchKernelGGL(drop_path_scales_kernel, dim3((S * B + 255) / 256), dim3(256), 0, (hipStream_t)stream, u, keep, S, B, out);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<drop_path_scales_kernel>(dim3((S * B + 255) / 256), dim3(256), 0, stream, u, keep, S, B, out);
 }
 
 extern "C" int gm3d_pad_cols(const void* src, long long lds, int R, int N, void* dst, int Np, int dtype, gm3d_stream_t stream) {
@@ -1354,14 +1283,11 @@ extern "C" int gm3d_pad_cols(const void* src, long long lds, int R, int N, void*
     if (N % 8 || Np % 8 || lds % 8) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     const size_t n = (size_t)R * (Np / 8);
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(pad_cols_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const bf16_t*)src, (size_t)lds, R,
-                                     N, (bf16_t*)dst, Np),
-                  hipLaunchKernelGGL(pad_cols_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)src, (size_t)lds, R, N,
-                                     (float*)dst, Np));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<pad_cols_kernel<T>>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const T*)src, (size_t)lds, R, N,
+                                              (T*)dst, Np);
+    });
 }
 
 extern "C" int gm3d_bn_finalize(const float* sums, double rows, const float* gamma, const float* beta, float eps,
@@ -1370,10 +1296,8 @@ extern "C" int gm3d_bn_finalize(const float* sums, double rows, const float* gam
     using namespace gm3d;
     if (!gamma || !beta || !running_mean || !running_var || !scale || !shift || !mean_out || !rstd_out || C < 1) return GM3D_EINVAL;
     if (training && (!sums || rows < 2.0)) return GM3D_EINVAL;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, sums, rows, gamma, beta, eps,
-                       momentum, running_mean, running_var, nbt, scale, shift, mean_out, rstd_out, C, training);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<bn_finalize_kernel>(dim3((C + 255) / 256), dim3(256), 0, stream, sums, rows, gamma, beta, eps, momentum,
+                                          running_mean, running_var, nbt, scale, shift, mean_out, rstd_out, C, training);
 }
 
 extern "C" int gm3d_pn1_finalize(const double* mom9, double rows, const float* w, const float* b, const float* gamma,
@@ -1383,20 +1307,15 @@ extern "C" int gm3d_pn1_finalize(const double* mom9, double rows, const float* w
     using namespace gm3d;
     if (!w || !b || !gamma || !beta || !running_mean || !running_var || !wf || !bf || !mean_out || !rstd_out || C < 1) return GM3D_EINVAL;
     if (training && (!mom9 || rows < 2.0)) return GM3D_EINVAL;
-    hipLaunchKernelGGL(pn1_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, mom9, rows, w, b, gamma, beta,
-                       eps, momentum, running_mean, running_var, nbt, wf, bf, mean_out, rstd_out, mcov, xmean, C, training);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<pn1_finalize_kernel>(dim3((C + 255) / 256), dim3(256), 0, stream, mom9, rows, w, b, gamma, beta, eps, momentum,
+                                           running_mean, running_var, nbt, wf, bf, mean_out, rstd_out, mcov, xmean, C, training);
 }
 
 extern "C" int gm3d_pn1_bwd_finalize(const double* q, const double* mcov, const float* w, const float* gamma, const float* rstd,
                                      float* dw, float* dgamma, float* dbeta, int C, gm3d_stream_t stream) {
     using namespace gm3d;
     if (!q || !mcov || !w || !gamma || !rstd || !dw || !dgamma || !dbeta || C < 1) return GM3D_EINVAL;
-    hipLaunchKernelGGL(pn1_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, q, mcov, w, gamma, rstd, dw,
-                       dgamma, dbeta, C);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<pn1_bwd_finalize_kernel>(dim3((C + 255) / 256), dim3(256), 0, stream, q, mcov, w, gamma, rstd, dw, dgamma, dbeta, C);
 }
 
 extern "C" int gm3d_mask_select_b(const float* loss_pred, const float* noise, int B, int L, int len_keep, int len_loss, float* mask,
@@ -1418,10 +1337,8 @@ extern "C" int gm3d_mask_select_b(const float* loss_pred, const float* noise, in
     if (L > GUIDED_NARROW)                                   // guided.hip: one workgroup per cloud
         return launch_mask_select_wide(loss_pred, noise, B, L, len_keep, len_loss, mask, mask_bool, vis_ids, mask_ids,
                                        id_pitch ? id_pitch : len_keep, id_pitch ? id_pitch : L - len_keep, stream);
-    hipLaunchKernelGGL(mask_select_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, loss_pred, noise, L, len_keep, len_loss,
-                       mask, vis_ids, mask_ids, id_pitch ? id_pitch : len_keep, id_pitch ? id_pitch : L - len_keep, mask_bool);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<mask_select_kernel>(dim3(B), dim3(64), 0, stream, loss_pred, noise, L, len_keep, len_loss,
+                                          mask, vis_ids, mask_ids, id_pitch ? id_pitch : len_keep, id_pitch ? id_pitch : L - len_keep, mask_bool);
 }
 
 extern "C" int gm3d_token_assemble_fwd(const void* tokens, const void* pos, const long long* order, int B, int L, int V, int C,
@@ -1432,14 +1349,11 @@ extern "C" int gm3d_token_assemble_fwd(const void* tokens, const void* pos, cons
     if (C % 8) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(token_assemble_fwd_kernel<bf16_t>, dim3(B * L), dim3(64), 0, st, (const bf16_t*)tokens,
-                                     (const bf16_t*)pos, order, L, V, C, (bf16_t*)x_vis, (bf16_t*)pos_vis, (bf16_t*)pos_full),
-                  hipLaunchKernelGGL(token_assemble_fwd_kernel<float>, dim3(B * L), dim3(64), 0, st, (const float*)tokens,
-                                     (const float*)pos, order, L, V, C, (float*)x_vis, (float*)pos_vis, (float*)pos_full));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<token_assemble_fwd_kernel<T>>(dim3(B * L), dim3(64), 0, stream, (const T*)tokens, (const T*)pos, order, L, V, C,
+                                                        (T*)x_vis, (T*)pos_vis, (T*)pos_full);
+    });
 }
 
 extern "C" int gm3d_token_assemble_bwd(const void* dx_vis, const void* dpos_vis, const void* dpos_full, const long long* order, int B,
@@ -1449,12 +1363,9 @@ extern "C" int gm3d_token_assemble_bwd(const void* dx_vis, const void* dpos_vis,
     if (C % 8) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
-    GM3D_DISPATCH(dtype,
-                  hipLaunchKernelGGL(token_assemble_bwd_kernel<bf16_t>, dim3(B * L), dim3(64), 0, st, (const bf16_t*)dx_vis,
-                                     (const bf16_t*)dpos_vis, (const bf16_t*)dpos_full, order, L, V, C, (bf16_t*)dtokens, (bf16_t*)dpos),
-                  hipLaunchKernelGGL(token_assemble_bwd_kernel<float>, dim3(B * L), dim3(64), 0, st, (const float*)dx_vis,
-                                     (const float*)dpos_vis, (const float*)dpos_full, order, L, V, C, (float*)dtokens, (float*)dpos));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<token_assemble_bwd_kernel<T>>(dim3(B * L), dim3(64), 0, stream, (const T*)dx_vis, (const T*)dpos_vis,
+                                                        (const T*)dpos_full, order, L, V, C, (T*)dtokens, (T*)dpos);
+    });
 }

@@ -176,10 +176,8 @@ __global__ void gather_points_grad_kernel(const float* __restrict__ gout, const 
 }
 
 template <int T, int PPT>
-static int launch_fps(const float* xyz, int B, int N, int npoint, int32_t* idx, float* centers, hipStream_t st) {
-    hipLaunchKernelGGL((fps_kernel<T, PPT>), dim3(B), dim3(T), 0, st, xyz, N, npoint, idx, centers);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+static int launch_fps(const float* xyz, int B, int N, int npoint, int32_t* idx, float* centers, gm3d_stream_t st) {
+    return launch_lds<fps_kernel<T, PPT>>(dim3(B), dim3(T), 0, st, xyz, N, npoint, idx, centers);
 }
 
 }  // namespace gm3d
@@ -190,15 +188,14 @@ extern "C" int gm3d_fps(const float* xyz, int B, int N, int npoint, int32_t* idx
     if (!xyz || !idx || B < 0 || N < 1 || npoint < 1) return GM3D_EINVAL;
     if (N > 16384) return GM3D_EUNSUPPORTED;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (N <= 256) return launch_fps<64, 4>(xyz, B, N, npoint, idx, centers, st);
+    if (N <= 256) return launch_fps<64, 4>(xyz, B, N, npoint, idx, centers, stream);
     // thread / points-per-thread shapes measured on MI355X (tools/fps_bench.py): the step is bound by one CU's VALU issue
     // plus the per-wave reduction chain, so large clouds prefer fewer, fatter waves
-    if (N <= 1024) return launch_fps<256, 4>(xyz, B, N, npoint, idx, centers, st);
-    if (N <= 2048) return launch_fps<256, 8>(xyz, B, N, npoint, idx, centers, st);
-    if (N <= 4096) return launch_fps<512, 8>(xyz, B, N, npoint, idx, centers, st);
-    if (N <= 8192) return launch_fps<512, 16>(xyz, B, N, npoint, idx, centers, st);
-    return launch_fps<1024, 16>(xyz, B, N, npoint, idx, centers, st);
+    if (N <= 1024) return launch_fps<256, 4>(xyz, B, N, npoint, idx, centers, stream);
+    if (N <= 2048) return launch_fps<256, 8>(xyz, B, N, npoint, idx, centers, stream);
+    if (N <= 4096) return launch_fps<512, 8>(xyz, B, N, npoint, idx, centers, stream);
+    if (N <= 8192) return launch_fps<512, 16>(xyz, B, N, npoint, idx, centers, stream);
+    return launch_fps<1024, 16>(xyz, B, N, npoint, idx, centers, stream);
 }
 
 extern "C" int gm3d_gather_points(const float* feat, const int32_t* idx, int B, int C, int N, int M,
@@ -208,9 +205,7 @@ extern "C" int gm3d_gather_points(const float* feat, const int32_t* idx, int B, 
     if (B == 0) return GM3D_OK;
     const size_t total = (size_t)B * C * M;
     const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(gather_points_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feat, idx, C, N, M, out, total);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<gather_points_kernel>(dim3(grid), dim3(256), 0, stream, feat, idx, C, N, M, out, total);
 }
 
 extern "C" int gm3d_gather_points_grad(const float* grad_out, const int32_t* idx, int B, int C, int N, int M,
@@ -221,8 +216,6 @@ extern "C" int gm3d_gather_points_grad(const float* grad_out, const int32_t* idx
     if (B == 0) return GM3D_OK;
     const size_t rows = (size_t)C * N;
     const int gx = (int)((rows + 255) / 256 < 1024 ? (rows + 255) / 256 : 1024);
-    hipLaunchKernelGGL(gather_points_grad_kernel, dim3(gx, B), dim3(256), (size_t)M * sizeof(int32_t),
-                       (hipStream_t)stream, grad_out, idx, C, N, M, grad_feat);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<gather_points_grad_kernel>(dim3(gx, B), dim3(256), (size_t)M * sizeof(int32_t), stream, grad_out, idx, C, N, M,
+                                                 grad_feat);
 }

@@ -86,10 +86,7 @@ extern "C" int gm3d_gather_inverse(const long long* idx, int B, int J, int S, in
     if (!idx || !off || !list || B < 0 || J < 1 || S < 1) return GM3D_EINVAL;
     if (S > 4096 || J > 16384) return GM3D_EUNSUPPORTED;
     if (B == 0) return GM3D_OK;
-    hipLaunchKernelGGL(gather_inverse_kernel, dim3(B), dim3(256), (size_t)(2 * S + 1) * sizeof(int), (hipStream_t)stream, idx, J, S, off,
-                       list);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<gather_inverse_kernel>(dim3(B), dim3(256), (size_t)(2 * S + 1) * sizeof(int), stream, idx, J, S, off, list);
 }
 
 extern "C" int gm3d_gather_rows_bwd(const void* dy, const int* off, const int* list, void* dx, int B, int J, int S, int C, int dtype,
@@ -101,13 +98,10 @@ extern "C" int gm3d_gather_rows_bwd(const void* dy, const int* off, const int* l
     if (B == 0) return GM3D_OK;
     const long long total = (long long)B * S * (C / 8);
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GM3D_BF16)
-        hipLaunchKernelGGL(gather_rows_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, off, list, (bf16_t*)dx, J, S, C, total);
-    else
-        hipLaunchKernelGGL(gather_rows_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, off, list, (float*)dx, J, S, C, total);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<gather_rows_bwd_kernel<T>>(dim3(grid), dim3(256), 0, stream, (const T*)dy, off, list, (T*)dx, J, S, C, total);
+    });
 }
 
 // ===================================================================== visible-first token order of a masked level
@@ -175,6 +169,12 @@ __global__ __launch_bounds__(256) void select_rows_kernel(const V* __restrict__ 
     }
 }
 
+// The row copies move 16 bytes at a time where rows and pointers allow it (`wide`), else one 4- or 2-byte element: calls f with a
+// null pointer to the unit, so that each copy states its launch once (`using V = std::remove_pointer_t<decltype(v)>;`).
+template <class F> int by_width(bool wide, int elem_bytes, F&& f) {
+    return wide ? f((uint4*)nullptr) : elem_bytes == 4 ? f((unsigned*)nullptr) : f((unsigned short*)nullptr);
+}
+
 }  // namespace gm3d
 
 extern "C" int gm3d_partition_visible(const unsigned char* masked, int B, int T, int Tc, int* perm_c, int* perm_v, int* inv_v, int* inv_m,
@@ -184,10 +184,8 @@ extern "C" int gm3d_partition_visible(const unsigned char* masked, int B, int T,
     if (T > 1024) return GM3D_EUNSUPPORTED;
     if (B == 0) return GM3D_OK;
     const int threads = (T + 63) / 64 * 64;
-    hipLaunchKernelGGL(partition_visible_kernel, dim3(B), dim3(threads), 0, (hipStream_t)stream, masked, T, Tc, perm_c, perm_v, inv_v, inv_m,
-                       vis_c, overflow);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<partition_visible_kernel>(dim3(B), dim3(threads), 0, stream, masked, T, Tc, perm_c, perm_v, inv_v, inv_m, vis_c,
+                                                overflow);
 }
 
 extern "C" int gm3d_select_rows(const void* a, const int* idx, const void* alt, void* out, int B, int Ta, int T, int C, int elem_bytes,
@@ -195,23 +193,16 @@ extern "C" int gm3d_select_rows(const void* a, const int* idx, const void* alt, 
     using namespace gm3d;
     if (!a || !idx || !out || B < 0 || Ta < 1 || T < 1 || C < 1 || (elem_bytes != 2 && elem_bytes != 4)) return GM3D_EINVAL;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const long long row_bytes = (long long)C * elem_bytes;
     const bool wide = row_bytes % 16 == 0 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)out % 16 == 0) && (!alt || (uintptr_t)alt % 16 == 0);
     const int cpr = wide ? (int)(row_bytes / 16) : C;
     const long long total = (long long)B * T * cpr;
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    if (wide)
-        hipLaunchKernelGGL(select_rows_kernel<uint4>, dim3(grid), dim3(256), 0, st, (const uint4*)a, idx, (const uint4*)alt, (uint4*)out, Ta, T,
-                           cpr, total);
-    else if (elem_bytes == 4)
-        hipLaunchKernelGGL(select_rows_kernel<unsigned>, dim3(grid), dim3(256), 0, st, (const unsigned*)a, idx, (const unsigned*)alt,
-                           (unsigned*)out, Ta, T, cpr, total);
-    else
-        hipLaunchKernelGGL(select_rows_kernel<unsigned short>, dim3(grid), dim3(256), 0, st, (const unsigned short*)a, idx,
-                           (const unsigned short*)alt, (unsigned short*)out, Ta, T, cpr, total);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_width(wide, elem_bytes, [&](auto* v) {
+        using V = std::remove_pointer_t<decltype(v)>;
+        return launch_lds<select_rows_kernel<V>>(dim3(grid), dim3(256), 0, stream, (const V*)a, idx, (const V*)alt, (V*)out, Ta, T, cpr,
+                                                 total);
+    });
 }
 
 // ===================================================================== token propagation (3-NN interpolation) of the hierarchical decoder
@@ -304,15 +295,11 @@ extern "C" int gm3d_interp3_fwd(const void* coarse, const long long* idx, const 
     if (B == 0) return GM3D_OK;
     const long long total = (long long)B * N * ((C1 + C2) / 8);
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GM3D_BF16)
-        hipLaunchKernelGGL(interp3_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)coarse, idx, w, (const bf16_t*)fine,
-                           (bf16_t*)out, N, S, C1, C2, total);
-    else
-        hipLaunchKernelGGL(interp3_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)coarse, idx, w, (const float*)fine,
-                           (float*)out, N, S, C1, C2, total);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<interp3_fwd_kernel<T>>(dim3(grid), dim3(256), 0, stream, (const T*)coarse, idx, w, (const T*)fine, (T*)out, N, S,
+                                                 C1, C2, total);
+    });
 }
 
 extern "C" int gm3d_gather_rows_bwd_w(const void* dy, int ldy, int col0, int refs_per_row, const float* w, const int* off, const int* list,
@@ -326,15 +313,11 @@ extern "C" int gm3d_gather_rows_bwd_w(const void* dy, int ldy, int col0, int ref
     if (B == 0) return GM3D_OK;
     const long long total = (long long)B * S * (C / 8);
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GM3D_BF16)
-        hipLaunchKernelGGL(gather_rows_bwd_w_kernel<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)dy, ldy, col0, refs_per_row, w, off,
-                           list, (bf16_t*)dx, J, S, C, total);
-    else
-        hipLaunchKernelGGL(gather_rows_bwd_w_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, ldy, col0, refs_per_row, w, off,
-                           list, (float*)dx, J, S, C, total);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<gather_rows_bwd_w_kernel<T>>(dim3(grid), dim3(256), 0, stream, (const T*)dy, ldy, col0, refs_per_row, w, off, list,
+                                                       (T*)dx, J, S, C, total);
+    });
 }
 
 extern "C" int gm3d_back_project(const unsigned char* masked_c, const long long* member, int B, int Gc, int k, int Gf,
@@ -343,10 +326,7 @@ extern "C" int gm3d_back_project(const unsigned char* masked_c, const long long*
     if (!masked_c || !member || !masked_f || B < 0 || Gc < 1 || k < 1 || Gf < 1) return GM3D_EINVAL;
     if (Gf > 8192) return GM3D_EUNSUPPORTED;
     if (B == 0) return GM3D_OK;
-    hipLaunchKernelGGL(back_project_kernel, dim3(B), dim3(256), (size_t)Gf * sizeof(int), (hipStream_t)stream, masked_c, member, Gc, k, Gf,
-                       masked_f);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<back_project_kernel>(dim3(B), dim3(256), (size_t)Gf * sizeof(int), stream, masked_c, member, Gc, k, Gf, masked_f);
 }
 
 // ===================================================================== row-wise choice by a per-token flag, gather by int64 lists
@@ -390,23 +370,16 @@ extern "C" int gm3d_where_rows(const unsigned char* flag, int invert, const void
     using namespace gm3d;
     if (!flag || !out || rows < 0 || C < 1 || (elem_bytes != 2 && elem_bytes != 4) || (alt_bcast && !alt)) return GM3D_EINVAL;
     if (rows == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const long long row_bytes = (long long)C * elem_bytes;
     const bool wide = row_bytes % 16 == 0 && ((uintptr_t)out % 16 == 0) && (!a || (uintptr_t)a % 16 == 0) && (!alt || (uintptr_t)alt % 16 == 0);
     const int cpr = wide ? (int)(row_bytes / 16) : C;
     const long long total = rows * cpr;
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    if (wide)
-        hipLaunchKernelGGL(where_rows_kernel<uint4>, dim3(grid), dim3(256), 0, st, flag, invert, (const uint4*)a, (const uint4*)alt, alt_bcast,
-                           (uint4*)out, cpr, total);
-    else if (elem_bytes == 4)
-        hipLaunchKernelGGL(where_rows_kernel<unsigned>, dim3(grid), dim3(256), 0, st, flag, invert, (const unsigned*)a, (const unsigned*)alt,
-                           alt_bcast, (unsigned*)out, cpr, total);
-    else
-        hipLaunchKernelGGL(where_rows_kernel<unsigned short>, dim3(grid), dim3(256), 0, st, flag, invert, (const unsigned short*)a,
-                           (const unsigned short*)alt, alt_bcast, (unsigned short*)out, cpr, total);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_width(wide, elem_bytes, [&](auto* v) {
+        using V = std::remove_pointer_t<decltype(v)>;
+        return launch_lds<where_rows_kernel<V>>(dim3(grid), dim3(256), 0, stream, flag, invert, (const V*)a, (const V*)alt, alt_bcast,
+                                                (V*)out, cpr, total);
+    });
 }
 
 extern "C" int gm3d_take_rows(const void* a, const long long* idx, void* out, int B, int S, int J, int C, int elem_bytes,
@@ -414,19 +387,13 @@ extern "C" int gm3d_take_rows(const void* a, const long long* idx, void* out, in
     using namespace gm3d;
     if (!a || !idx || !out || B < 0 || S < 1 || J < 1 || C < 1 || (elem_bytes != 2 && elem_bytes != 4)) return GM3D_EINVAL;
     if (B == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const long long row_bytes = (long long)C * elem_bytes;
     const bool wide = row_bytes % 16 == 0 && ((uintptr_t)a % 16 == 0) && ((uintptr_t)out % 16 == 0);
     const int cpr = wide ? (int)(row_bytes / 16) : C;
     const long long total = (long long)B * J * cpr;
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    if (wide)
-        hipLaunchKernelGGL(take_rows_kernel<uint4>, dim3(grid), dim3(256), 0, st, (const uint4*)a, idx, (uint4*)out, S, J, cpr, total);
-    else if (elem_bytes == 4)
-        hipLaunchKernelGGL(take_rows_kernel<unsigned>, dim3(grid), dim3(256), 0, st, (const unsigned*)a, idx, (unsigned*)out, S, J, cpr, total);
-    else
-        hipLaunchKernelGGL(take_rows_kernel<unsigned short>, dim3(grid), dim3(256), 0, st, (const unsigned short*)a, idx, (unsigned short*)out,
-                           S, J, cpr, total);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_width(wide, elem_bytes, [&](auto* v) {
+        using V = std::remove_pointer_t<decltype(v)>;
+        return launch_lds<take_rows_kernel<V>>(dim3(grid), dim3(256), 0, stream, (const V*)a, idx, (V*)out, S, J, cpr, total);
+    });
 }

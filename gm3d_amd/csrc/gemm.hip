@@ -472,9 +472,7 @@ extern "C" int gm3d_transpose_bf16_multi(int count, const void* const* src, void
         if (first > 0x7ffffff0LL) return GM3D_EUNSUPPORTED;
     }
     for (int j = count; j < TR_MAXP; ++j) m.p[j] = m.p[0];
-    hipLaunchKernelGGL(transpose_bf16_multi_kernel, dim3((unsigned)first), dim3(256), 0, (hipStream_t)stream, m);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<transpose_bf16_multi_kernel>(dim3((unsigned)first), dim3(256), 0, stream, m);
 }
 
 extern "C" int gm3d_transpose_bf16_batched(const void* src, void* dst, int batch, int rows, int cols, long long src_batch_stride,
@@ -483,8 +481,6 @@ extern "C" int gm3d_transpose_bf16_batched(const void* src, void* dst, int batch
     if (!src || !dst || batch < 0 || rows < 1 || cols < 1 || src_batch_stride < (long long)rows * cols) return GM3D_EINVAL;
     if (rows % 8 || cols % 8 || batch > 65535) return GM3D_EUNSUPPORTED;
     if (batch == 0) return GM3D_OK;
-    hipLaunchKernelGGL(transpose_bf16_kernel, dim3((cols + 63) / 64, (rows + 63) / 64, batch), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src,
-                       (bf16_t*)dst, rows, cols, (size_t)src_batch_stride);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<transpose_bf16_kernel>(dim3((cols + 63) / 64, (rows + 63) / 64, batch), dim3(256), 0, stream, (const bf16_t*)src,
+                                             (bf16_t*)dst, rows, cols, (size_t)src_batch_stride);
 }

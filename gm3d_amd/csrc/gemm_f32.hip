@@ -262,14 +262,10 @@ extern "C" int gm3d_gemm_tn_f32(const float* A, const float* W, const float* bia
     if (total > 0x7ffffff0LL) return GM3D_EUNSUPPORTED;
     const int grid = (int)((total + 7) / 8 * 8);
     const int vec_a = (((size_t)A & 15) == 0 && lda % 4 == 0), vec_w = (((size_t)W & 15) == 0 && ldw % 4 == 0);
-    if (small)
-        hipLaunchKernelGGL(gemm_tn_f32_kernel<1>, dim3(grid), dim3(F_THREADS), 0, (hipStream_t)stream, A, W, bias, C, M, N, K, lda, ldw,
-                           ldc, (int)tn, (int)total, vec_a, vec_w);
-    else
-        hipLaunchKernelGGL(gemm_tn_f32_kernel<2>, dim3(grid), dim3(F_THREADS), 0, (hipStream_t)stream, A, W, bias, C, M, N, K, lda, ldw,
-                           ldc, (int)tn, (int)total, vec_a, vec_w);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_int<1, 2>(bm / 64, [&](auto mi) {
+        return launch_lds<gemm_tn_f32_kernel<decltype(mi)::value>>(dim3(grid), dim3(F_THREADS), 0, stream, A, W, bias, C, M, N, K, lda, ldw,
+                                                                   ldc, (int)tn, (int)total, vec_a, vec_w);
+    });
 }
 
 extern "C" int gm3d_gemm_nt_f32_splits(int batch, int R, int N, int K) {
@@ -305,21 +301,16 @@ extern "C" int gm3d_gemm_nt_f32(const float* dY, const float* X, float* out, flo
     const int grid = (int)((total + 7) / 8 * 8);
     const int vec_y = (((size_t)dY & 15) == 0 && ldy % 4 == 0 && (batch == 1 || stride_y % 4 == 0));
     const int vec_x = (((size_t)X & 15) == 0 && ldx % 4 == 0 && (batch == 1 || stride_x % 4 == 0));
-    hipStream_t st = (hipStream_t)stream;
-    if (splits == 1) {
-        hipLaunchKernelGGL(gemm_nt_f32_kernel, dim3(grid), dim3(F_THREADS), 0, st, dY, X, out, R, N, K, ldy, ldx, ldo, stride_y, stride_x,
-                           stride_o, 0LL, 1, slab, tn_, tk_, (int)total, vec_y, vec_x, accumulate ? 1 : 0);
-        GM3D_CHECK_LAUNCH();
-        return GM3D_OK;
-    }
+    if (splits == 1)
+        return launch_lds<gemm_nt_f32_kernel>(dim3(grid), dim3(F_THREADS), 0, stream, dY, X, out, R, N, K, ldy, ldx, ldo, stride_y, stride_x,
+                                              stride_o, 0LL, 1, slab, tn_, tk_, (int)total, vec_y, vec_x, accumulate ? 1 : 0);
     const long long nk = (long long)N * K;
-    hipLaunchKernelGGL(gemm_nt_f32_kernel, dim3(grid), dim3(F_THREADS), 0, st, dY, X, part, R, N, K, ldy, ldx, (long long)K, stride_y,
-                       stride_x, (long long)splits * nk, nk, splits, slab, tn_, tk_, (int)total, vec_y, vec_x, 0);
-    GM3D_CHECK_LAUNCH();
+    const int rc = launch_lds<gemm_nt_f32_kernel>(dim3(grid), dim3(F_THREADS), 0, stream, dY, X, part, R, N, K, ldy, ldx, (long long)K,
+                                                  stride_y, stride_x, (long long)splits * nk, nk, splits, slab, tn_, tk_, (int)total, vec_y,
+                                                  vec_x, 0);
+    if (rc != GM3D_OK) return rc;
     const long long per_batch = (long long)batch * nk;
     const long long blocks = (per_batch + 255) / 256;
-    hipLaunchKernelGGL(nt_f32_slab_sum_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, part, out, splits, N, K,
-                       ldo, stride_o, per_batch, accumulate ? 1 : 0);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<nt_f32_slab_sum_kernel>(dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, part, out, splits, N, K,
+                                              ldo, stride_o, per_batch, accumulate ? 1 : 0);
 }

@@ -519,13 +519,10 @@ extern "C" int gm3d_gemm_nt_bf16_multi(int count, const void* const* dY, const v
     const size_t lds = (size_t)NT_NBUF * NT_STAGE;
     const int rc = launch_lds<gemm_nt_multi_kernel>(dim3((unsigned)first), dim3(256), lds, stream, m);
     if (rc != GM3D_OK) return rc;
-    if (sm.count > 0) {
-        if (max_batch > 65535) return GM3D_EUNSUPPORTED;
-        const int gx = (int)((max_cols4 + 255) / 256 < 256 ? (max_cols4 + 255) / 256 : 256);
-        hipLaunchKernelGGL(nt_sum_multi_kernel, dim3(gx, sm.count, max_batch), dim3(256), 0, (hipStream_t)stream, sm);
-        GM3D_CHECK_LAUNCH();
-    }
-    return GM3D_OK;
+    if (sm.count == 0) return GM3D_OK;
+    if (max_batch > 65535) return GM3D_EUNSUPPORTED;
+    const int gx = (int)((max_cols4 + 255) / 256 < 256 ? (max_cols4 + 255) / 256 : 256);
+    return launch_lds<nt_sum_multi_kernel>(dim3(gx, sm.count, max_batch), dim3(256), 0, stream, sm);
 }
 
 extern "C" int gm3d_gemm_nt_tiles(int N, int K) { return N < 1 || K < 1 ? 0 : ((N + 127) / 128) * ((K + 127) / 128); }

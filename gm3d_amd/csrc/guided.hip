@@ -108,17 +108,13 @@ int launch_mask_select_wide(const float* loss_pred, const float* noise, int B, i
                             unsigned char* mask_bool, long long* vis_ids, long long* mask_ids, int vis_pitch, int mask_pitch,
                             gm3d_stream_t stream) {
     if (L <= GUIDED_NARROW || L > GUIDED_MAX) return GM3D_EUNSUPPORTED;
-    hipLaunchKernelGGL(mask_select_wide_kernel, dim3(B), dim3(wide_threads(L)), 0, (hipStream_t)stream, loss_pred, noise, L, len_keep,
-                       len_loss, mask, vis_ids, mask_ids, vis_pitch, mask_pitch, mask_bool);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<mask_select_wide_kernel>(dim3(B), dim3(wide_threads(L)), 0, stream, loss_pred, noise, L, len_keep, len_loss, mask,
+                                               vis_ids, mask_ids, vis_pitch, mask_pitch, mask_bool);
 }
 
 int launch_rank_loss_wide(const float* pred, int ldp, const float* target, int B, int M, float* out, float* dpred, gm3d_stream_t stream) {
     if (M <= GUIDED_NARROW || M > GUIDED_MAX) return GM3D_EUNSUPPORTED;
-    hipLaunchKernelGGL(rank_loss_wide_kernel, dim3(B), dim3(wide_threads(M)), 0, (hipStream_t)stream, pred, ldp, target, M, out, dpred);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<rank_loss_wide_kernel>(dim3(B), dim3(wide_threads(M)), 0, stream, pred, ldp, target, M, out, dpred);
 }
 
 }  // namespace gm3d

@@ -325,10 +325,7 @@ extern "C" int gm3d_knn_probe_normalize(const float* X, int n, int d, float* Y, 
     if (n < 0 || d < 1) return GM3D_EINVAL;
     if (n == 0) return GM3D_OK;
     if (!X || !Y) return GM3D_EINVAL;
-    hipLaunchKernelGGL(knn_probe_normalize_kernel, dim3((n + NORM_ROWS - 1) / NORM_ROWS), dim3(NORM_THREADS), 0, (hipStream_t)stream, X,
-                       n, d, Y);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<knn_probe_normalize_kernel>(dim3((n + NORM_ROWS - 1) / NORM_ROWS), dim3(NORM_THREADS), 0, stream, X, n, d, Y);
 }
 
 extern "C" int gm3d_knn_probe_neighbours(const float* Xn, const float* Qn, int n, int m, int d, int k, int* idx, float* sim,

@@ -454,8 +454,6 @@ extern "C" int gm3d_linprobe_eval(const float* Q, const long long* yq, int m, in
     const int rc = check_shape(m, d, ncls);
     if (rc != GM3D_OK || m == 0) return rc;
     if (!Q || !W || !bias || !running_mean || !running_var || (yq && !correct)) return GM3D_EINVAL;
-    hipLaunchKernelGGL(linprobe_eval_kernel, dim3((m + LE_ROWS - 1) / LE_ROWS), dim3(LE_THREADS), 0, (hipStream_t)stream, Q, yq, m, d,
-                       ncls, W, bias, running_mean, running_var, logits, pred, reinterpret_cast<unsigned long long*>(correct));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<linprobe_eval_kernel>(dim3((m + LE_ROWS - 1) / LE_ROWS), dim3(LE_THREADS), 0, stream, Q, yq, m, d, ncls, W, bias,
+                                            running_mean, running_var, logits, pred, reinterpret_cast<unsigned long long*>(correct));
 }

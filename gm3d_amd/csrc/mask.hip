@@ -67,8 +67,6 @@ extern "C" int gm3d_mask_centers(const float* keys_or_center, const int* start, 
     if (num_mask < 0 || num_mask >= G || id_pitch < G) return GM3D_EINVAL;
     if (B == 0) return GM3D_OK;
     const int threads = (G + 63) / 64 * 64;
-    hipLaunchKernelGGL(mask_centers_kernel, dim3(B), dim3(threads), 0, (hipStream_t)stream, keys_or_center, start, mode, G, num_mask,
-                       mask_bool, order, id_pitch);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<mask_centers_kernel>(dim3(B), dim3(threads), 0, stream, keys_or_center, start, mode, G, num_mask, mask_bool, order,
+                                           id_pitch);
 }

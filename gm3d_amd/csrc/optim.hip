@@ -114,17 +114,14 @@ extern "C" int gm3d_adamw_ema_flat_step_lrd(float* params, const float* grads, f
     if (!params || !grads || !exp_avg || !exp_avg_sq || !lr_dev || !step_dev || !partial || !scal || n < 4) return GM3D_EINVAL;
     if ((n & 3) || (n_decay & 3) || n_decay < 0 || n_decay > n) return GM3D_EINVAL;
     if (ema && !ema_w_dev) return GM3D_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     const int grid = flat_grid(n);
-    hipLaunchKernelGGL(flat_sumsq_kernel, dim3(grid), dim3(256), 0, st, grads, n, partial);
-    GM3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(optim_prep_kernel, dim3(1), dim3(256), 0, st, partial, grid, max_norm, step_dev, beta1, beta2, scal);
-    GM3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(adamw_ema_flat_kernel, dim3(grid), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, ema,
-                       (bf16_t*)shadow_p, (bf16_t*)shadow_e, n, n_decay, lr_dev, weight_decay, beta1, beta2, eps, ema_w_dev, scal,
-                       lr_scale);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    int rc = launch_lds<flat_sumsq_kernel>(dim3(grid), dim3(256), 0, stream, grads, n, partial);
+    if (rc != GM3D_OK) return rc;
+    rc = launch_lds<optim_prep_kernel>(dim3(1), dim3(256), 0, stream, partial, grid, max_norm, step_dev, beta1, beta2, scal);
+    if (rc != GM3D_OK) return rc;
+    return launch_lds<adamw_ema_flat_kernel>(dim3(grid), dim3(256), 0, stream, params, grads, exp_avg, exp_avg_sq, ema, (bf16_t*)shadow_p,
+                                             (bf16_t*)shadow_e, n, n_decay, lr_dev, weight_decay, beta1, beta2, eps, ema_w_dev, scal,
+                                             lr_scale);
 }
 
 extern "C" int gm3d_adamw_ema_flat_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* ema,

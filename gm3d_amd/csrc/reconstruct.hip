@@ -97,17 +97,6 @@ __global__ __launch_bounds__(RA_WAVES* GM3D_WAVE) void reconstruct_assemble_kern
     }
 }
 
-template <class T, bool VEC>
-static void ra_launch(const void* pred, long long pred_bstride, const float* neighborhood, const float* center, const long long* vis_ids,
-                      long long vis_stride, const long long* mask_ids, long long mask_stride, int B, int G, int k, int V, int M,
-                      int layout, float* dense, float* full_center, hipStream_t st) {
-    const int P = B * G;
-    const int blocks = (P + RA_WAVES - 1) / RA_WAVES < RA_MAX_BLOCKS ? (P + RA_WAVES - 1) / RA_WAVES : RA_MAX_BLOCKS;
-    hipLaunchKernelGGL((reconstruct_assemble_kernel<T, VEC>), dim3(blocks), dim3(RA_WAVES * GM3D_WAVE), 0, st, (const T*)pred,
-                       (size_t)pred_bstride, neighborhood, center, vis_ids, (size_t)vis_stride, mask_ids, (size_t)mask_stride, B, G, k,
-                       V, M, layout, dense, full_center);
-}
-
 constexpr int RP_WAVES = 4, RP_LANES = 16, RP_TOKENS = RP_WAVES * GM3D_WAVE / RP_LANES, RP_MAX_G = 8192,
               RP_MAX_CHUNKS = RP_MAX_G / GM3D_WAVE;
 
@@ -167,11 +156,12 @@ __global__ __launch_bounds__(RP_WAVES* GM3D_WAVE) void reconstruct_partition_ker
 }
 
 template <class T, bool VEC, bool PRED>
-static void rp_launch(const void* pred, const float* neighborhood, const float* center, const unsigned char* masked, int B, int G, int k,
-                      float* dense, float* full_center, int* order, int* n_visible, hipStream_t st) {
+static int rp_launch(const void* pred, const float* neighborhood, const float* center, const unsigned char* masked, int B, int G, int k,
+                     float* dense, float* full_center, int* order, int* n_visible, gm3d_stream_t st) {
     const int slices = (G + RP_TOKENS - 1) / RP_TOKENS;      // B * slices <= B * G < 2^31 / 3: a valid grid
-    hipLaunchKernelGGL((reconstruct_partition_kernel<T, VEC, PRED>), dim3((unsigned)B * slices), dim3(RP_WAVES * GM3D_WAVE), 0, st,
-                       (const T*)pred, neighborhood, center, masked, G, k, slices, dense, full_center, order, n_visible);
+    return launch_lds<reconstruct_partition_kernel<T, VEC, PRED>>(dim3((unsigned)B * slices), dim3(RP_WAVES * GM3D_WAVE), 0, st,
+                                                                  (const T*)pred, neighborhood, center, masked, G, k, slices, dense,
+                                                                  full_center, order, n_visible);
 }
 
 }  // namespace gm3d
@@ -193,18 +183,17 @@ extern "C" int gm3d_reconstruct_assemble(const void* pred, long long pred_bstrid
     // 16-byte accesses need 16-byte patch rows everywhere: k % 4 == 0, aligned bases, and a pred batch stride of whole 4-element units
     const bool vec = k % 4 == 0 && ((uintptr_t)neighborhood | (uintptr_t)dense) % 16 == 0 &&
                      (M == 0 || ((uintptr_t)pred % (4 * esz) == 0 && pred_bstride % 4 == 0));
-    hipStream_t st = (hipStream_t)stream;
-#define GM3D_RA(T, VEC)                                                                                                             \
-    ra_launch<T, VEC>(pred, pred_bstride, neighborhood, center, vis_ids, vis_stride, mask_ids, mask_stride, B, G, k, V, M, layout, \
-                      dense, full_center, st)
-    if (dtype == GM3D_BF16) {
-        if (vec) GM3D_RA(bf16_t, true); else GM3D_RA(bf16_t, false);
-    } else {
-        if (vec) GM3D_RA(float, true); else GM3D_RA(float, false);
-    }
-#undef GM3D_RA
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    const int P = B * G;
+    const int blocks = (P + RA_WAVES - 1) / RA_WAVES < RA_MAX_BLOCKS ? (P + RA_WAVES - 1) / RA_WAVES : RA_MAX_BLOCKS;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        auto launch = [&](auto v) {                        // v: std::true_type for the 16-byte form
+            return launch_lds<reconstruct_assemble_kernel<T, decltype(v)::value>>(
+                dim3(blocks), dim3(RA_WAVES * GM3D_WAVE), 0, stream, (const T*)pred, (size_t)pred_bstride, neighborhood, center, vis_ids,
+                (size_t)vis_stride, mask_ids, (size_t)mask_stride, B, G, k, V, M, layout, dense, full_center);
+        };
+        return vec ? launch(std::true_type{}) : launch(std::false_type{});
+    });
 }
 
 extern "C" int gm3d_reconstruct_partition(const void* pred, const float* neighborhood, const float* center, const unsigned char* masked,
@@ -220,17 +209,11 @@ extern "C" int gm3d_reconstruct_partition(const void* pred, const float* neighbo
     const size_t esz = dtype == GM3D_BF16 ? 2 : 4;
     // 16-byte accesses need 16-byte patch rows everywhere: k % 4 == 0 and aligned bases (pred rows are dense: 3k elements)
     const bool vec = k % 4 == 0 && ((uintptr_t)neighborhood | (uintptr_t)dense) % 16 == 0 && (!pred || (uintptr_t)pred % (4 * esz) == 0);
-    hipStream_t st = (hipStream_t)stream;
+    // (element type, PRED) takes three of its four combinations, so this instance table stays a macro
 #define GM3D_RP(T, VEC, PRED) \
-    rp_launch<T, VEC, PRED>(pred, neighborhood, center, masked, B, G, k, dense, full_center, order, n_visible, st)
-    if (!pred) {
-        if (vec) GM3D_RP(float, true, false); else GM3D_RP(float, false, false);
-    } else if (dtype == GM3D_BF16) {
-        if (vec) GM3D_RP(bf16_t, true, true); else GM3D_RP(bf16_t, false, true);
-    } else {
-        if (vec) GM3D_RP(float, true, true); else GM3D_RP(float, false, true);
-    }
+    rp_launch<T, VEC, PRED>(pred, neighborhood, center, masked, B, G, k, dense, full_center, order, n_visible, stream)
+    if (!pred) return vec ? GM3D_RP(float, true, false) : GM3D_RP(float, false, false);
+    if (dtype == GM3D_BF16) return vec ? GM3D_RP(bf16_t, true, true) : GM3D_RP(bf16_t, false, true);
+    return vec ? GM3D_RP(float, true, true) : GM3D_RP(float, false, true);
 #undef GM3D_RP
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
 }

@@ -627,15 +627,11 @@ extern "C" int gm3d_residual_ln_fwd(const float* res, const void* y, const float
     if (C != LNC) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if (R == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GM3D_BF16)
-        hipLaunchKernelGGL(residual_ln_fwd_kernel<bf16_t>, dim3(ln_fwd_grid(R)), dim3(256), 0, st, res, (const bf16_t*)y, bias,
-                           rowscale, rows_per_sample, (const bf16_t*)add, gamma, beta, eps, out_res, (bf16_t*)h, mean, rstd, R);
-    else
-        hipLaunchKernelGGL(residual_ln_fwd_kernel<float>, dim3(ln_fwd_grid(R)), dim3(256), 0, st, res, (const float*)y, bias,
-                           rowscale, rows_per_sample, (const float*)add, gamma, beta, eps, out_res, (float*)h, mean, rstd, R);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<residual_ln_fwd_kernel<T>>(dim3(ln_fwd_grid(R)), dim3(256), 0, stream, res, (const T*)y, bias, rowscale,
+                                                     rows_per_sample, (const T*)add, gamma, beta, eps, out_res, (T*)h, mean, rstd, R);
+    });
 }
 
 extern "C" int gm3d_residual_ln_bwd(const void* dh, const float* gin, const float* x, const float* mean,
@@ -649,15 +645,11 @@ extern "C" int gm3d_residual_ln_bwd(const void* dh, const float* gin, const floa
     if (C != LNC) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if (R == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GM3D_BF16)
-        hipLaunchKernelGGL(residual_ln_bwd_kernel<bf16_t>, dim3(ln_grid(R)), dim3(256), 0, st, (const bf16_t*)dh, gin, x, mean,
-                           rstd, gamma, rowscale, rows_per_sample, dx, (bf16_t*)dy, acc, (bf16_t*)acc_out, partial, R);
-    else
-        hipLaunchKernelGGL(residual_ln_bwd_kernel<float>, dim3(ln_grid(R)), dim3(256), 0, st, (const float*)dh, gin, x, mean,
-                           rstd, gamma, rowscale, rows_per_sample, dx, (float*)dy, acc, (float*)acc_out, partial, R);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<residual_ln_bwd_kernel<T>>(dim3(ln_grid(R)), dim3(256), 0, stream, (const T*)dh, gin, x, mean, rstd, gamma,
+                                                     rowscale, rows_per_sample, dx, (T*)dy, acc, (T*)acc_out, partial, R);
+    });
 }
 
 extern "C" int gm3d_ln_plain_partial_rows(int R) { return R < 1 ? 0 : gm3d::ln_grid(R); }
@@ -683,16 +675,15 @@ extern "C" int gm3d_add_ln_fwd(const void* x, const void* y, const float* ybias,
     if (C < 4 || C % 4 || C > 512) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if (R == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     const int nq = (C + 127) / 128;
-#define GM3D_LNP_F(T_, NQ_) hipLaunchKernelGGL((ln_plain_fwd_kernel<T_, NQ_>), dim3(ln_fwd_grid(R)), dim3(256), 0, st, (const T_*)x, gamma, \
-                                               beta, eps, (T_*)h, mean, rstd, R, C, (const T_*)y, ybias, rowscale, rows_per_sample,      \
-                                               (const T_*)z, (T_*)s_out)
-    if (dtype == GM3D_BF16) { if (nq == 1) GM3D_LNP_F(bf16_t, 1); else if (nq == 2) GM3D_LNP_F(bf16_t, 2); else if (nq == 3) GM3D_LNP_F(bf16_t, 3); else GM3D_LNP_F(bf16_t, 4); }
-    else { if (nq == 1) GM3D_LNP_F(float, 1); else if (nq == 2) GM3D_LNP_F(float, 2); else if (nq == 3) GM3D_LNP_F(float, 3); else GM3D_LNP_F(float, 4); }
-#undef GM3D_LNP_F
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return by_int<1, 2, 3, 4>(nq, [&](auto q) {
+            return launch_lds<ln_plain_fwd_kernel<T, decltype(q)::value>>(dim3(ln_fwd_grid(R)), dim3(256), 0, stream, (const T*)x, gamma,
+                                                                          beta, eps, (T*)h, mean, rstd, R, C, (const T*)y, ybias, rowscale,
+                                                                          rows_per_sample, (const T*)z, (T*)s_out);
+        });
+    });
 }
 
 extern "C" int gm3d_add_ln_bwd_acc(const void* dh, const void* gin, const void* x, const float* mean, const float* rstd, const float* gamma,
@@ -724,26 +715,22 @@ extern "C" int gm3d_add_ln_bwd_acc(const void* dh, const void* gin, const void* 
     if ((nsum != 2 && nsum != 3) || (rowscale && (!dy || rows_per_sample < 1))) return GM3D_EINVAL;
     if (C < 4 || C % 4 || C > 512) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     const int nq = (C + 127) / 128;
-#define GM3D_LNP_B(T_, NQ_) hipLaunchKernelGGL((ln_plain_bwd_kernel<T_, NQ_>), dim3(ln_grid(R)), dim3(256), 0, st, (const T_*)dh, (const T_*)x, \
-                                               mean, rstd, gamma, (T_*)dx, partial, R, C, (const T_*)gin, rowscale, rows_per_sample,     \
-                                               (T_*)dy, nsum, (T_*)acc, acc_mode)
-    if (dtype == GM3D_BF16) { if (nq == 1) GM3D_LNP_B(bf16_t, 1); else if (nq == 2) GM3D_LNP_B(bf16_t, 2); else if (nq == 3) GM3D_LNP_B(bf16_t, 3); else GM3D_LNP_B(bf16_t, 4); }
-    else { if (nq == 1) GM3D_LNP_B(float, 1); else if (nq == 2) GM3D_LNP_B(float, 2); else if (nq == 3) GM3D_LNP_B(float, 3); else GM3D_LNP_B(float, 4); }
-#undef GM3D_LNP_B
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return by_int<1, 2, 3, 4>(nq, [&](auto q) {
+            return launch_lds<ln_plain_bwd_kernel<T, decltype(q)::value>>(dim3(ln_grid(R)), dim3(256), 0, stream, (const T*)dh, (const T*)x,
+                                                                          mean, rstd, gamma, (T*)dx, partial, R, C, (const T*)gin, rowscale,
+                                                                          rows_per_sample, (T*)dy, nsum, (T*)acc, acc_mode);
+        });
+    });
 }
 
 extern "C" int gm3d_colsum_finish(const float* partial, int nrows, int pitch, int ncols, float* out, int accumulate,
                                   gm3d_stream_t stream) {
     using namespace gm3d;
     if (!partial || !out || nrows < 0 || ncols < 1 || pitch < ncols) return GM3D_EINVAL;
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3((ncols + 31) / 32), dim3(256), 0, (hipStream_t)stream, partial, nrows,
-                       pitch, ncols, out, accumulate);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<colsum_finish_kernel>(dim3((ncols + 31) / 32), dim3(256), 0, stream, partial, nrows, pitch, ncols, out, accumulate);
 }
 
 extern "C" int gm3d_bias_gelu_fwd(const void* f, const float* bias, void* g, int R, int C, int dtype,
@@ -755,13 +742,10 @@ extern "C" int gm3d_bias_gelu_fwd(const void* f, const float* bias, void* g, int
     if (R == 0) return GM3D_OK;
     const int cap = R >= 32768 ? 8192 : 4096;          // one wave per workgroup at C = 384: 32 of them fit a CU
     int grid = (R + 1) / 2; grid = grid > cap ? cap : grid;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == GM3D_BF16)
-        hipLaunchKernelGGL(bias_gelu_fwd_kernel<bf16_t>, dim3(grid), dim3(C / 8), 0, st, (const bf16_t*)f, bias, (bf16_t*)g, R, C);
-    else
-        hipLaunchKernelGGL(bias_gelu_fwd_kernel<float>, dim3(grid), dim3(C / 8), 0, st, (const float*)f, bias, (float*)g, R, C);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<bias_gelu_fwd_kernel<T>>(dim3(grid), dim3(C / 8), 0, stream, (const T*)f, bias, (T*)g, R, C);
+    });
 }
 
 extern "C" int gm3d_bias_gelu_bwd(const void* dg, const void* f, const float* bias, void* df, float* partial, int R,
@@ -771,17 +755,13 @@ extern "C" int gm3d_bias_gelu_bwd(const void* dg, const void* f, const float* bi
     if (C % 8 || C / 8 > 1024) return GM3D_EUNSUPPORTED;
     if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
     if (R == 0) return GM3D_OK;
-    hipStream_t st = (hipStream_t)stream;
     int SL = 1024 / (C / 8); SL = SL > 4 ? 4 : SL;
     const size_t lds = (size_t)SL * C * sizeof(float);
-    if (dtype == GM3D_BF16)
-        hipLaunchKernelGGL(bias_gelu_bwd_kernel<bf16_t>, dim3(gelu_bwd_grid(R)), dim3(C / 8, SL), lds, st, (const bf16_t*)dg,
-                           (const bf16_t*)f, bias, (bf16_t*)df, partial, R, C);
-    else
-        hipLaunchKernelGGL(bias_gelu_bwd_kernel<float>, dim3(gelu_bwd_grid(R)), dim3(C / 8, SL), lds, st, (const float*)dg,
-                           (const float*)f, bias, (float*)df, partial, R, C);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return by_dtype(dtype, [&](auto* t) {
+        using T = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<bias_gelu_bwd_kernel<T>>(dim3(gelu_bwd_grid(R)), dim3(C / 8, SL), lds, stream, (const T*)dg, (const T*)f, bias,
+                                                   (T*)df, partial, R, C);
+    });
 }
 
 extern "C" int gm3d_colsum_finish_batched(const float* partial, int njobs, long long job_stride, int nrows, int pitch,
@@ -790,10 +770,8 @@ extern "C" int gm3d_colsum_finish_batched(const float* partial, int njobs, long 
     if (!partial || !out || njobs < 1 || nrows < 0 || ncols < 1 || pitch < ncols || job_stride < 0 || out_stride < ncols)
         return GM3D_EINVAL;
     if (njobs > 65535) return GM3D_EUNSUPPORTED;
-    hipLaunchKernelGGL(colsum_finish_batched_kernel, dim3((ncols + 31) / 32, njobs), dim3(256), 0, (hipStream_t)stream, partial,
-                       (size_t)job_stride, nrows, pitch, ncols, out, out_stride);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<colsum_finish_batched_kernel>(dim3((ncols + 31) / 32, njobs), dim3(256), 0, stream, partial, (size_t)job_stride,
+                                                    nrows, pitch, ncols, out, out_stride);
 }
 
 extern "C" int gm3d_sum_few_rows(const float* partial, int njobs, int nrows, long long ncols, float* out, gm3d_stream_t stream) {
@@ -802,7 +780,5 @@ extern "C" int gm3d_sum_few_rows(const float* partial, int njobs, int nrows, lon
     if (ncols % 4 || njobs > 65535 || nrows > 64) return GM3D_EUNSUPPORTED;
     const size_t n4 = (size_t)ncols / 4;
     int gx = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(sum_few_rows_kernel, dim3(gx, njobs), dim3(256), 0, (hipStream_t)stream, partial, nrows, n4, out);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<sum_few_rows_kernel>(dim3(gx, njobs), dim3(256), 0, stream, partial, nrows, n4, out);
 }

@@ -477,9 +477,7 @@ extern "C" int gm3d_svm_gram(const float* X, int n, int d, double* K, gm3d_strea
     if (!X || !K || n < 1 || d < 1) return GM3D_EINVAL;
     if (n > SVM_MAX_N || d > SVM_MAX_D) return GM3D_EUNSUPPORTED;
     const long long T = (n + GRAM_TILE - 1) / GRAM_TILE;
-    hipLaunchKernelGGL(svm_gram_kernel, dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, (hipStream_t)stream, X, n, d, K);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<svm_gram_kernel>(dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, stream, X, n, d, K);
 }
 
 extern "C" int gm3d_svm_smo(const double* K, int n, int ncls, const int* class_start, double C, double tol, long long max_iter,
@@ -506,10 +504,7 @@ extern "C" int gm3d_svm_weights(const float* X, int n, int d, int ncls, const in
     if (rc != GM3D_OK) return rc;
     if (!X || !alpha || !w || d < 1) return GM3D_EINVAL;
     if (d > SVM_MAX_D) return GM3D_EUNSUPPORTED;
-    hipLaunchKernelGGL(svm_weights_kernel, dim3(ncls * (ncls - 1) / 2, (d + 255) / 256), dim3(256), 0, (hipStream_t)stream, X, d,
-                       ncls, cs, alpha, w);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<svm_weights_kernel>(dim3(ncls * (ncls - 1) / 2, (d + 255) / 256), dim3(256), 0, stream, X, d, ncls, cs, alpha, w);
 }
 
 extern "C" int gm3d_svm_predict(const float* X, int m, int d, int ncls, const double* w, const double* rho, const long long* labels,
@@ -518,8 +513,6 @@ extern "C" int gm3d_svm_predict(const float* X, int m, int d, int ncls, const do
     if (ncls < 2 || ncls > SVM_MAX_CLS || d > SVM_MAX_D || m > SVM_MAX_N) return GM3D_EUNSUPPORTED;
     if (m == 0) return GM3D_OK;
     if (!X || !w || !rho || !pred || (labels && !correct)) return GM3D_EINVAL;
-    hipLaunchKernelGGL(svm_predict_kernel, dim3((m + PRED_ROWS - 1) / PRED_ROWS), dim3(PRED_THREADS), 0, (hipStream_t)stream, X, m, d,
-                       ncls, w, rho, labels, pred, reinterpret_cast<unsigned long long*>(correct));
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<svm_predict_kernel>(dim3((m + PRED_ROWS - 1) / PRED_ROWS), dim3(PRED_THREADS), 0, stream, X, m, d, ncls, w, rho,
+                                          labels, pred, reinterpret_cast<unsigned long long*>(correct));
 }

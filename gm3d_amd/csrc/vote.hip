@@ -271,10 +271,8 @@ extern "C" int gm3d_vote_sample(const float* points, const int32_t* fps_idx, con
     if (total * 3 > (1LL << 40)) return GM3D_EUNSUPPORTED;
     const long long want = (total + 255) / 256;
     const int grid = (int)(want < 8192 ? want : 8192);
-    hipLaunchKernelGGL(vote_sample_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, points, fps_idx, subsets, scale, shift, B, N0,
-                       point_all, npoints, total, out);
-    GM3D_CHECK_LAUNCH();
-    return GM3D_OK;
+    return launch_lds<vote_sample_kernel>(dim3(grid), dim3(256), 0, stream, points, fps_idx, subsets, scale, shift, B, N0, point_all,
+                                          npoints, total, out);
 }
 
 extern "C" int gm3d_cls_tail_vote(const void* x, int V, int B, int T, int C, const float* W1, const float* b1, const float* g1,
@@ -291,11 +289,11 @@ extern "C" int gm3d_cls_tail_vote(const void* x, int V, int B, int T, int C, con
     const HeadArgs h{W1, b1, g1, be1, rm1, rv1, W2, b2, g2, be2, rm2, rv2, W3, b3};
     const size_t lds = (size_t)(V * 2 * TAIL_C + TAIL_TG * TAIL_C + V * TAIL_H) * sizeof(float);
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(correct);
-    if (dtype == GM3D_BF16)
-        return launch_lds<cls_tail_vote_kernel<bf16_t>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const bf16_t*)x, V, B, T, h, cls_dim, eps,
-                                                        labels, mean, pred, cnt, votes);
-    return launch_lds<cls_tail_vote_kernel<float>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const float*)x, V, B, T, h, cls_dim, eps,
-                                                   labels, mean, pred, cnt, votes);
+    return by_dtype(dtype, [&](auto* t) {
+        using E = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<cls_tail_vote_kernel<E>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const E*)x, V, B, T, h, cls_dim, eps, labels,
+                                                   mean, pred, cnt, votes);
+    });
 }
 
 extern "C" int gm3d_cls_tail_vote_pool(const void* x, int V, int B, int T, int C, int mode, const float* W1, const float* b1,
@@ -316,9 +314,9 @@ extern "C" int gm3d_cls_tail_vote_pool(const void* x, int V, int B, int T, int C
     const int F = mode ? 2 * TAIL_C : TAIL_C;
     const size_t lds = (size_t)(V * F + V * TAIL_H) * sizeof(float);     // 64 KiB at V = 16, F = 768
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(correct);
-    if (dtype == GM3D_BF16)
-        return launch_lds<cls_tail_vote_pool_kernel<bf16_t>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const bf16_t*)x, V, B, T, mode, h,
-                                                             cls_dim, eps, labels, mean, pred, cnt, votes, feat);
-    return launch_lds<cls_tail_vote_pool_kernel<float>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const float*)x, V, B, T, mode, h,
-                                                        cls_dim, eps, labels, mean, pred, cnt, votes, feat);
+    return by_dtype(dtype, [&](auto* t) {
+        using E = std::remove_pointer_t<decltype(t)>;
+        return launch_lds<cls_tail_vote_pool_kernel<E>>(dim3(B), dim3(TAIL_THREADS), lds, stream, (const E*)x, V, B, T, mode, h, cls_dim,
+                                                        eps, labels, mean, pred, cnt, votes, feat);
+    });
 }

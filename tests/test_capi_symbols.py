@@ -29,6 +29,51 @@ def test_library_exports_every_declared_symbol():
     assert b"invalid" in _capi.lib.gm3d_strerror(-1)
 
 
+HEADER_TEXT = """
+typedef void *gm3d_stream_t; /* hipStream_t */
+#define GM3D_OK 0
+/* a comment (with a parenthesis); int gm3d_not_declared(int x); */
+int gm3d_version(void);
+const char *gm3d_name(int code);   // line comment (also stripped)
+int gm3d_every_kind(const void *p, float *q, const long long *ids, int n, float s, double d,
+                    long long stride, gm3d_stream_t stream);
+"""
+
+
+def test_header_parser_maps_every_parameter_kind():
+    from gm3d_amd import _capi
+    c = ctypes
+    assert _capi.parse_header(HEADER_TEXT) == {
+        "gm3d_version": (c.c_int, []),
+        "gm3d_name": (c.c_char_p, [c.c_int]),
+        "gm3d_every_kind": (c.c_int, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_float, c.c_double, c.c_longlong, c.c_void_p]),
+    }
+
+
+def test_header_parser_refuses_unknown_types():
+    import pytest
+    from gm3d_amd import _capi
+    with pytest.raises(ImportError, match=r"gm3d_f.*unsigned"):
+        _capi.parse_header("int gm3d_f(unsigned n);")
+    with pytest.raises(ImportError, match=r"gm3d_g.*size_t"):
+        _capi.parse_header("int gm3d_g(int n, size_t bytes, gm3d_stream_t stream);")
+    with pytest.raises(ImportError, match=r"gm3d_h.*float"):
+        _capi.parse_header("float gm3d_h(int n);")
+    with pytest.raises(ImportError, match=r"gm3d_i.*void"):
+        _capi.parse_header("void gm3d_i(int n);")
+
+
+def test_signature_widths_come_from_the_header():
+    """Pins that an argument-count check cannot see: a 64-bit stride, a double and a float, and the one string result."""
+    from gm3d_amd import _capi
+    assert _capi.SIGNATURES["gm3d_colsum_finish_batched"][2] is ctypes.c_longlong
+    assert _capi.SIGNATURES["gm3d_bn_finalize"][1] is ctypes.c_double
+    assert _capi.SIGNATURES["gm3d_attention_fwd"][6] is ctypes.c_float
+    assert _capi.lib.gm3d_strerror.restype is ctypes.c_char_p
+    assert _capi.lib.gm3d_abi_version.restype is ctypes.c_int
+    assert _capi.lib.gm3d_bn_finalize.argtypes[1] is ctypes.c_double
+
+
 def test_argument_errors_are_detected_before_any_launch():
     """NULL pointers / bad sizes return GM3D_EINVAL / EUNSUPPORTED on the host: safe without a GPU."""
     from gm3d_amd._capi import lib, GM3D_EINVAL, GM3D_EUNSUPPORTED
