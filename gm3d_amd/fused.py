@@ -18,7 +18,7 @@ import weakref
 import torch
 
 from ._capi import lib
-from . import attention_pad, gemm, wgrads
+from . import attention, gemm, wgrads
 from . import streams as _streams
 from .gemm import bias_gelu_bwd, bias_gelu_fwd  # noqa: F401  (their home is beside the products they follow)
 from .ops import _launch, _ptr, _stream, _DT
@@ -161,51 +161,6 @@ def finish_batched(partial, out):
     return out
 
 
-def _attention_fwd(qkv, B, T, H, scale, out=None):
-    if out is None:
-        out = torch.empty(B * T, H * 64, dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
-    if T > 128:      # more tokens than one workgroup's LDS images hold (cfgs/config_3.yaml: 256 groups): the flash-style kernel of
-        #              the hierarchical encoder with no mask (same qkv / out / lse layouts; T > 512: its streaming form, T <= 2048)
-        #              bf16 between what its LDS holds and 513 tokens: the streaming form at 513 rows, the padding blocked as keys; the
-        #              lse that comes back is then (B,H,513) and goes to _attention_bwd as it is (attention_pad.py)
-        return attention_pad.forward(qkv, out, lse, B, T, H, scale)
-    _launch("gm3d_attention_fwd", {"B": B, "T": T, "H": H, "dtype": str(qkv.dtype)}, lib.gm3d_attention_fwd, _ptr(qkv),
-            _ptr(out), _ptr(lse), B, T, H, float(scale), _DT[qkv.dtype], _stream())
-    return out, lse
-
-
-def _attention_qkv_fwd(h, wqkv, B, T, H, scale, out=None, want_qkv=False, want_lse=False):
-    """qkv projection + attention in one launch (csrc/attention.hip attn_qkv_fwd_bf16_kernel); returns (out, lse|None, qkv|None)."""
-    C = h.shape[1]
-    if out is None:
-        out = torch.empty(B * T, C, dtype=h.dtype, device=h.device)
-    lse = torch.empty(B, H, T, dtype=torch.float32, device=h.device) if want_lse else None
-    qkv = torch.empty(B * T, 3 * C, dtype=h.dtype, device=h.device) if want_qkv else None
-    _launch("gm3d_attention_qkv_fwd", {"B": B, "T": T, "H": H, "C": C, "dtype": str(h.dtype)}, lib.gm3d_attention_qkv_fwd, _ptr(h),
-            _ptr(wqkv), _ptr(out), _ptr(lse) if want_lse else None, _ptr(qkv) if want_qkv else None, B, T, H, C, float(scale),
-            _DT[h.dtype], _stream())
-    return out, lse, qkv
-
-
-def attention_qkv_supported(h, wqkv, T, H):
-    return (h.is_cuda and h.dtype == torch.bfloat16 and wqkv.dtype == torch.bfloat16 and T <= 64 and h.shape[1] == 384 == H * 64
-            and h.is_contiguous() and wqkv.is_contiguous() and tuple(wqkv.shape) == (1152, 384)
-            and h.data_ptr() % 16 == 0 and wqkv.data_ptr() % 16 == 0)
-
-
-def _attention_bwd(qkv, out, dout, lse, B, T, H, scale, dqkv=None):
-    if dqkv is None:
-        dqkv = torch.empty_like(qkv)
-    if T > 128:
-        # the flash-style kernel, its streaming form from 513 tokens, or (bf16, 257..512 tokens) the streaming form on padded operands
-        # (attention_pad.py)
-        return attention_pad.backward(qkv, out, dout, lse, dqkv, B, T, H, scale)
-    _launch("gm3d_attention_bwd", {"B": B, "T": T, "H": H, "dtype": str(qkv.dtype)}, lib.gm3d_attention_bwd, _ptr(qkv),
-            _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), B, T, H, float(scale), _DT[qkv.dtype], _stream())
-    return dqkv
-
-
 DIRECT_INPUT_GRADS = True   # the stack backward writes dx / dpos in the activation type itself (no converting copies)
 FUSE_QKV_ATTENTION = True   # qkv GEMM + attention forward as one launch (bf16, 32 < T <= 64)
 PER_BLOCK = 11  # ln1.w ln1.b qkv.w proj.w proj.b ln2.w ln2.b fc1.w fc1.b fc2.w fc2.b
@@ -279,7 +234,7 @@ class TransformerStackFn(torch.autograd.Function):
                     qkv, m1, r1 = gemm.linear_lna(u16, st1, ln1w, ln1b, eps, weight_cache.get(wqkv, adt), None,
                                                   h_out=H1[i] if need else None, want_stats=need)
                 yield
-                a, lse = _attention_fwd(qkv, B, T, H, scale, out=A[i] if need else None)
+                a, lse = attention.fwd(qkv, None, B, T, H, 64, scale, out=A[i] if need else None, head=True, pad=True)
                 yield
                 x1, x16, st2 = gemm.linear_res(a, weight_cache.get(wproj, adt), bproj, u, dp1, T, None)
                 yield
@@ -300,13 +255,13 @@ class TransformerStackFn(torch.autograd.Function):
             u, h1, m1, r1 = residual_ln_fwd(res, y, bias, rs, T, posa, ln1w, ln1b, eps, adt, R, h=H1[i] if need else None)
             yield
             Wq = weight_cache.get(wqkv, adt)
-            if FUSE_QKV_ATTENTION and T > 32 and attention_qkv_supported(h1, Wq, T, H):
+            if attention.route_qkv(h1, Wq, T, H, FUSE_QKV_ATTENTION):
                 # q|k|v never leave the CU in the no-grad (teacher) pass; with a backward to come they are written on the side
-                a, lse, qkv = _attention_qkv_fwd(h1, Wq, B, T, H, scale, out=A[i] if need else None, want_qkv=need, want_lse=need)
+                a, lse, qkv = attention.qkv_fwd(h1, Wq, B, T, H, scale, out=A[i] if need else None, want_qkv=need, want_lse=need)
             else:
                 qkv = gemm.mm(h1, Wq)
                 yield
-                a, lse = _attention_fwd(qkv, B, T, H, scale, out=A[i] if need else None)
+                a, lse = attention.fwd(qkv, None, B, T, H, 64, scale, out=A[i] if need else None, head=True, pad=True)
             yield
             p = gemm.mm(a, weight_cache.get(wproj, adt))
             yield
@@ -401,7 +356,7 @@ class TransformerStackFn(torch.autograd.Function):
             gi[5], gi[6], gi[4] = SLN[2 * i + 1, 0], SLN[2 * i + 1, 1], SLN[2 * i + 1, 2]
             # attention branch: x1 = u + dp1 * (a @ Wproj^T + bproj)
             da = gemm.mm(d_p, WPT[i]) if fuse_mlp_bwd else gemm.mm_nn(d_p, weight_cache.get(wproj, adt))
-            dqkv = _attention_bwd(qkv, A[i], da, lse, B, T, H, scale, dqkv=DQ[i])
+            dqkv = attention.bwd(qkv, None, A[i], da, lse, B, T, H, 64, scale, dqkv=DQ[i], head=True, pad=True)
             dh1 = gemm.mm(dqkv, WQT[i]) if fuse_mlp_bwd else gemm.mm_nn(dqkv, weight_cache.get(wqkv, adt))
             last = DIRECT_INPUT_GRADS and i == 0 and nblk > 1 and adt != torch.float32 and ctx.in_dtypes == (adt, adt)
             if last:

@@ -23,10 +23,10 @@ attention sees the same allowed keys in the same relative order); filler rows ar
 import torch
 
 from ._capi import lib
-from . import fused, gemm, wgrads
+from . import attention, fused, gemm, wgrads
 from .embed import _c32
 from .fused import PER_BLOCK, block_params, weight_cache  # noqa: F401
-from .ops import _DT, _launch, _ptr, _stream, launch_masked_attention
+from .ops import _DT, _launch, _ptr, _stream
 
 
 # ----------------------------------------------------------------------------- kernel wrappers
@@ -56,23 +56,6 @@ def _add_ln_bwd(dh, gin, x, mean, rstd, gamma, rowscale, rps, dy, partial, adt, 
             _ptr(rstd), _ptr(gamma), _ptr(rowscale), int(rps), _ptr(dx), _ptr(dy), _ptr(partial), 3, _ptr(acc), int(acc_mode), R, C,
             _DT[adt], _stream())
     return dx
-
-
-def _attn_fwd(qkv, bits, B, T, H, hd, scale, out):
-    if bits is None and hd == 64 and T <= 128:
-        return fused._attention_fwd(qkv, B, T, H, scale, out=out)
-    lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
-    launch_masked_attention(False, {"B": B, "T": T, "H": H, "HD": hd, "dtype": str(qkv.dtype)},
-                            _ptr(qkv), _ptr(bits), _ptr(out), _ptr(lse), B, T, H, hd, float(scale), _DT[qkv.dtype], _stream())
-    return out, lse
-
-
-def _attn_bwd(qkv, a, da, lse, bits, B, T, H, hd, scale, dqkv):
-    if bits is None and hd == 64 and T <= 128:
-        return fused._attention_bwd(qkv, a, da, lse, B, T, H, scale, dqkv=dqkv)
-    launch_masked_attention(True, {"B": B, "T": T, "H": H, "HD": hd, "dtype": str(qkv.dtype)},
-                            _ptr(qkv), _ptr(bits), _ptr(a), _ptr(da), _ptr(lse), _ptr(dqkv), B, T, H, hd, float(scale), _DT[qkv.dtype], _stream())
-    return dqkv
 
 
 FUSE_GELU = True          # widths 192 / 384: bias + GELU (forward) and GELU' + bias-gradient partials (backward) in the GEMM epilogues (tests flip it)
@@ -117,7 +100,7 @@ class MaskedStackFn(torch.autograd.Function):
             dp1, dp2 = meta["dp"][i]
             s1, h1, m1, r1 = _add_ln_fwd(s, y, yb, rs, T, posa, _c32(ln1w), _c32(ln1b), eps, adt, True, H1[i] if need else None)
             qkv = gemm.mm(h1, weight_cache.get(wqkv, adt))
-            a, lse = _attn_fwd(qkv, bits, B, T, H, hd, scale, A[i] if need else torch.empty(R, C, dtype=adt, device=dev))
+            a, lse = attention.fwd(qkv, bits, B, T, H, hd, scale, out=A[i] if need else None, head=True, pad=False)
             p = gemm.mm(a, weight_cache.get(wproj, adt))
             s2, h2, m2, r2 = _add_ln_fwd(s1, p, _c32(bproj), dp1, T, None, _c32(ln2w), _c32(ln2b), eps, adt, True, H2[i] if need else None)
             W1 = weight_cache.get(w1, adt)
@@ -178,7 +161,7 @@ class MaskedStackFn(torch.autograd.Function):
             G = _add_ln_bwd(dh2, G, s2, m2, r2, _c32(ln2w), meta["dp"][i][0], T, DP[i], PLN[2 * i + 1], adt)
             gi[5], gi[6], gi[4] = SLN[2 * i + 1, :C], SLN[2 * i + 1, C:2 * C], SLN[2 * i + 1, 2 * C:]
             da = gemm.mm(DP[i], WPT[i])
-            _attn_bwd(qkv, A[i], da, lse, bits, B, T, H, hd, scale, DQ[i])
+            attention.bwd(qkv, bits, A[i], da, lse, B, T, H, hd, scale, dqkv=DQ[i], head=True, pad=False)
             dh1 = gemm.mm(DQ[i], WQT[i])
             G = _add_ln_bwd(dh1, G, s1, m1, r1, _c32(ln1w), meta["dp"][i - 1][1] if i > 0 else None, T, DO[i - 1] if i > 0 else None,
                             PLN[2 * i], adt, acc=dpos, acc_mode=1 if i == nblk - 1 else 2)

@@ -477,42 +477,11 @@ class ChamferDistanceL1(torch.nn.Module):
 _DT = {torch.float32: _capi.GM3D_F32, torch.bfloat16: _capi.GM3D_BF16}
 
 
-class _Attention(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, num_heads, scale):
-        qkv = qkv.contiguous()
-        if qkv.dtype not in _DT:
-            raise RuntimeError("attention supports float32 and bfloat16, got %s" % qkv.dtype)
-        _require(qkv, None, "qkv")
-        B, T, C3 = qkv.shape
-        if C3 != 3 * num_heads * 64:
-            raise RuntimeError("qkv last dim must be 3*num_heads*64")
-        out = torch.empty(B, T, num_heads * 64, dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty(B, num_heads, T, dtype=torch.float32, device=qkv.device)
-        _launch("gm3d_attention_fwd", {"B": B, "T": T, "H": num_heads, "dtype": str(qkv.dtype)}, lib.gm3d_attention_fwd, _ptr(qkv), _ptr(out), _ptr(lse), B, T, num_heads, float(scale),
-                                     _DT[qkv.dtype], _stream())
-        ctx.save_for_backward(qkv, out, lse)
-        ctx.num_heads, ctx.scale = num_heads, float(scale)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
-        dout = dout.contiguous().to(qkv.dtype)
-        B, T, _ = qkv.shape
-        dqkv = torch.empty_like(qkv)
-        _launch("gm3d_attention_bwd", {"B": B, "T": T, "H": ctx.num_heads, "dtype": str(qkv.dtype)}, lib.gm3d_attention_bwd, _ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), B, T, ctx.num_heads,
-                                     ctx.scale, _DT[qkv.dtype], _stream())
-        return dqkv, None, None
-
-
 def attention(qkv, num_heads, scale):
     """qkv (B,T,3*H*64) = output of the qkv Linear (timm layout (B,T,3,H,64)) -> (B,T,H*64).  T <= 128: one workgroup per (cloud,
     head) with the whole head in LDS; 128 < T <= 512 (cfgs/config_3.yaml: 256 groups): the flash-style kernel of the hierarchical
     encoder without a mask; 513 <= T <= 2048 (the 8k recipe: 512 groups + the class token): its streaming form."""
-    if qkv.shape[1] > 128:
-        return _AttentionMasked.apply(qkv, None, num_heads, scale)
-    return _Attention.apply(qkv, num_heads, scale)
+    return _attention.AttentionFn.apply(qkv, None, num_heads, scale, True, True)
 
 
 def pack_mask(mask):
@@ -549,53 +518,11 @@ def radius_mask_bits(center, vis, radius, masked=None):
     return bits
 
 
-def launch_masked_attention(backward, dims, *args):
-    """Launches the masked attention for dims["T"] tokens: gm3d_attention_masked_* hold a head in LDS (T <= 512),
-    gm3d_attention_long_* stream it (513 <= T <= 2048); same arguments, one owner per range."""
-    name = "gm3d_attention_%s_%s" % ("long" if dims["T"] > 512 else "masked", "bwd" if backward else "fwd")
-    _launch(name, dims, getattr(lib, name), *args)
-
-
-class _AttentionMasked(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, bits, num_heads, scale):
-        qkv = qkv.contiguous()
-        if qkv.dtype not in _DT:
-            raise RuntimeError("attention supports float32 and bfloat16, got %s" % qkv.dtype)
-        _require(qkv, None, "qkv")
-        B, T, C3 = qkv.shape
-        hd = C3 // (3 * num_heads)
-        if C3 != 3 * num_heads * hd or hd not in (16, 32, 64):
-            raise RuntimeError("qkv last dim must be 3*num_heads*head_dim with head_dim 16, 32 or 64")
-        if bits is not None and (bits.dtype != torch.int32 or tuple(bits.shape) != (B, T, (T + 31) // 32) or not bits.is_contiguous()
-                                 or not bits.is_cuda):
-            raise RuntimeError("mask bitset must be a contiguous int32 (B,T,ceil(T/32)) GPU tensor (ops.pack_mask)")
-        out = torch.empty(B, T, num_heads * hd, dtype=qkv.dtype, device=qkv.device)
-        lse = torch.empty(B, num_heads, T, dtype=torch.float32, device=qkv.device)
-        launch_masked_attention(False, {"B": B, "T": T, "H": num_heads, "HD": hd, "dtype": str(qkv.dtype)},
-                                _ptr(qkv), _ptr(bits), _ptr(out), _ptr(lse), B, T, num_heads, hd, float(scale),
-                                _DT[qkv.dtype], _stream())
-        ctx.save_for_backward(qkv, out, lse, bits)
-        ctx.num_heads, ctx.scale, ctx.hd = num_heads, float(scale), hd
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        qkv, out, lse, bits = ctx.saved_tensors
-        dout = dout.contiguous().to(qkv.dtype)
-        B, T, _ = qkv.shape
-        dqkv = torch.empty_like(qkv)
-        launch_masked_attention(True, {"B": B, "T": T, "H": ctx.num_heads, "HD": ctx.hd, "dtype": str(qkv.dtype)},
-                                _ptr(qkv), _ptr(bits), _ptr(out), _ptr(dout), _ptr(lse), _ptr(dqkv), B, T,
-                                ctx.num_heads, ctx.hd, ctx.scale, _DT[qkv.dtype], _stream())
-        return dqkv, None, None, None
-
-
 def attention_masked(qkv, bits, num_heads, scale):
     """qkv (B,T,3*H*hd), hd in {16,32,64}, T <= 2048; bits = pack_mask(mask) of a SYMMETRIC (B,T,T) bool mask (True = not allowed)
     or None -> (B,T,H*hd).  A query with no allowed key yields zeros.  (The hierarchical Point-M2AE encoder's attention.)
     T <= 512: the head sits in LDS (csrc/attention_masked.hip); 513 <= T <= 2048: it streams through (csrc/attention_long.hip)."""
-    return _AttentionMasked.apply(qkv, bits, num_heads, scale)
+    return _attention.AttentionFn.apply(qkv, bits, num_heads, scale, False, False)
 
 
 # ------------------------------------------------------------------ reconstructed clouds (models/Point_MAE.py:428-439)
@@ -683,3 +610,7 @@ def reconstruct_partition(pred, neighborhood, center, masked):
             _ptr(pred), _ptr(neighborhood), _ptr(center), _ptr(masked), B, G, k, dt, _ptr(dense), _ptr(full_center), _ptr(order),
             _ptr(n_visible), _stream())
     return dense, full_center, order, n_visible
+
+
+# which kernel runs attention, and the autograd node of the two ops above; at the end: it imports this module's helpers
+from . import attention as _attention  # noqa: E402

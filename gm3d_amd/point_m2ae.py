@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import attention
 from . import models_mae_learn_loss as M
 from . import ops
 from . import streams
@@ -209,11 +210,7 @@ class MaskedAttention(nn.Module):
 
     def forward(self, x, bits, proj_bias=True):
         qkv = self.qkv(x)
-        hd = x.shape[-1] // self.num_heads
-        if bits is None and hd == 64 and x.shape[1] <= 128:
-            a = ops.attention(qkv, self.num_heads, self.scale)              # the Point-MAE kernel (whole head in one workgroup)
-        else:
-            a = ops.attention_masked(qkv, bits, self.num_heads, self.scale)
+        a = attention.AttentionFn.apply(qkv, bits, self.num_heads, self.scale, True, False)      # head: the Point-MAE kernel may run
         return self.proj(a) if proj_bias else _linear(a, self.proj.weight, None)
 
 

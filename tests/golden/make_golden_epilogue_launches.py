@@ -115,11 +115,11 @@ def _run(fn, inputs, train, bf16):
         torch.cuda.synchronize()
 
 
-def _stack(B, dtype, train):
+def _stack(B, dtype, train, T=64, depth=2):
     from gm3d_amd import fused
     from gm3d_amd import models_mae_learn_loss as M
     torch.manual_seed(0)
-    dec = M.TransformerDecoder(embed_dim=384, depth=2, drop_path_rate=0.0, num_heads=6).cuda().train(train)
+    dec = M.TransformerDecoder(embed_dim=384, depth=depth, drop_path_rate=0.0, num_heads=6).cuda().train(train)
     # bf16 shadows of the blocks' weights at a constant stride in ONE buffer, like the flat optimizer's: whether the backward's
     # transposing launch takes them must not depend on where the allocator happens to put separately cast copies
     ws = [[p for p in fused.block_params(b) if p.dim() == 2] for b in dec.blocks]
@@ -131,7 +131,7 @@ def _stack(B, dtype, train):
             shadow = flat[off:off + p.numel()].view_as(p).copy_(p.detach())
             fused.weight_cache.pin_view(p, shadow)
             off += p.numel()
-    _run(lambda x, pos: fused.run_stack(dec.blocks, dec.norm, x, pos, train), [_randn(1, B, 64, 384), _randn(2, B, 64, 384)], train,
+    _run(lambda x, pos: fused.run_stack(dec.blocks, dec.norm, x, pos, train), [_randn(1, B, T, 384), _randn(2, B, T, 384)], train,
          dtype == "bf16")
 
 

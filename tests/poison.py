@@ -224,13 +224,13 @@ def scan_sites():
 
 # ------------------------------------------------------------------------------------------------------------------ coverage
 CASES = {}         # test module -> (cases that ran to their end, cases it has): filled by the two GPU modules
-HOT = ("gm3d_amd/gemm.py", "gm3d_amd/embed.py", "gm3d_amd/fused.py", "gm3d_amd/ops.py", "gm3d_amd/heads.py")
+HOT = ("gm3d_amd/gemm.py", "gm3d_amd/embed.py", "gm3d_amd/fused.py", "gm3d_amd/ops.py", "gm3d_amd/heads.py", "gm3d_amd/attention.py")
 UNREACHED = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "poison_unreached.json")
 
 
 def coverage(complete):
     """The coverage condition over SITES, the union of what this process poisoned.  tests/golden/poison_unreached.json names the
-    allocation lines no case reaches, {site: {"reason": ..., "switch": ...}}: at most 15 % of the scanned lines; none in gemm / embed /
+    allocation lines no case reaches, {site: {"reason": ..., "switch": ...}}: at most 15 % of the scanned lines; none in gemm / embed / attention /
     fused / ops / heads unless behind a switch that is off by default, which is named; none that IS reached (the list cannot rot).
     complete (every poison case of the process ran): every scanned line is reached or listed.  -> (scanned, reached, listed) counts."""
     with open(UNREACHED) as f:

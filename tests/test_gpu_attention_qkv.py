@@ -10,16 +10,16 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("B,T", [(1, 64), (3, 25), (5, 1), (2, 33), (64, 64), (7, 63), (128, 64)])
 @pytest.mark.parametrize("train", [False, True])
 def test_fused_equals_two_launches(B, T, train):
-    from gm3d_amd import fused, gemm
+    from gm3d_amd import attention, gemm
     H, C = 6, 384
     g = torch.Generator().manual_seed(B * 100 + T)
     h = torch.randn(B * T, C, generator=g).cuda().bfloat16()
     w = (torch.randn(3 * C, C, generator=g) * 0.06).cuda().bfloat16()
-    assert fused.attention_qkv_supported(h, w, T, H)
+    assert attention.qkv_supported(h, w, T, H)
     scale = 0.125
     qkv_ref = gemm.linear_tn_ring(h, w, bm=64)
-    a_ref, lse_ref = fused._attention_fwd(qkv_ref, B, T, H, scale)
-    a, lse, qkv = fused._attention_qkv_fwd(h, w, B, T, H, scale, want_qkv=train, want_lse=train)
+    a_ref, lse_ref = attention.fwd(qkv_ref, None, B, T, H, 64, scale, head=True, pad=True)
+    a, lse, qkv = attention.qkv_fwd(h, w, B, T, H, scale, want_qkv=train, want_lse=train)
     torch.cuda.synchronize()
     assert torch.equal(a, a_ref)
     if train:
@@ -34,11 +34,11 @@ def test_fused_equals_two_launches(B, T, train):
 
 
 def test_unsupported_shapes_are_refused():
-    from gm3d_amd import fused
+    from gm3d_amd import attention
     from gm3d_amd._capi import Gm3dError
     h = torch.zeros(65, 384, device="cuda", dtype=torch.bfloat16)
     w = torch.zeros(1152, 384, device="cuda", dtype=torch.bfloat16)
     with pytest.raises(Gm3dError):
-        fused._attention_qkv_fwd(h, w, 1, 65, 6, 0.125)
+        attention.qkv_fwd(h, w, 1, 65, 6, 0.125)
     with pytest.raises(Gm3dError):
-        fused._attention_qkv_fwd(h.float(), w.float(), 1, 65, 6, 0.125)
+        attention.qkv_fwd(h.float(), w.float(), 1, 65, 6, 0.125)

@@ -426,17 +426,17 @@ def test_wide_launches_write_all_they_return(pattern):
 @pytest.mark.parametrize("T", [257, 400, 481, 512])
 def test_stack_attention_between_the_lds_and_the_streaming_lengths(T):
     """bf16, head_dim 64: the LDS-resident attention holds 480 tokens forward and 256 backward and the streaming kernels start at 513;
-    the stacks run the lengths in between on the streaming kernels at 513 rows with the padding blocked as keys (fused._attention_fwd /
-    _attention_bwd).  Against softmax(Q K^T / 8) V in fp64 with the project's bf16 attention bars (tests/test_gpu_abi_edges.py: output
+    the stacks run the lengths in between on the streaming kernels at 513 rows with the padding blocked as keys (attention.fwd / bwd with
+    pad=True).  Against softmax(Q K^T / 8) V in fp64 with the project's bf16 attention bars (tests/test_gpu_abi_edges.py: output
     2e-2, gradient 3e-2 of the reference's maximum); the forward below 481 is the LDS kernel's as before."""
-    from gm3d_amd import attention_pad, fused
+    from gm3d_amd import attention
     B, H, hd = 2, 6, 64
     g = torch.Generator(device="cuda").manual_seed(T)
     qkv = torch.randn(B * T, 3 * H * hd, device="cuda", generator=g).to(torch.bfloat16)
     dout = torch.randn(B * T, H * hd, device="cuda", generator=g).to(torch.bfloat16)
-    out, lse = fused._attention_fwd(qkv, B, T, H, hd ** -0.5)
-    assert tuple(lse.shape) == (B, H, T if T <= 480 else attention_pad.PAD_T)
-    dqkv = fused._attention_bwd(qkv, out, dout, lse, B, T, H, hd ** -0.5)
+    out, lse = attention.fwd(qkv, None, B, T, H, hd, hd ** -0.5, head=True, pad=True)
+    assert tuple(lse.shape) == (B, H, T if T <= 480 else attention.PAD_T)
+    dqkv = attention.bwd(qkv, None, out, dout, lse, B, T, H, hd, hd ** -0.5, head=True, pad=True)
     q64 = qkv.double().requires_grad_(True)
     q, k, v = q64.view(B, T, 3, H, hd).permute(2, 0, 3, 1, 4)
     ref = (torch.softmax(q @ k.transpose(-1, -2) * hd ** -0.5, dim=-1) @ v).transpose(1, 2).reshape(B * T, H * hd)

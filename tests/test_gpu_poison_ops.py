@@ -229,14 +229,14 @@ for _dt in DTYPES:
 for _B, _T in [(1, 1), (2, 33)]:
     @case("attention_qkv_fused-B%d-T%d" % (_B, _T))
     def _(B=_B, T=_T):
-        from gm3d_amd import fused
+        from gm3d_amd import attention
         H = 6                        # the fused qkv + attention forward: bf16, C = 384, T <= 64
         g = gen(33 + T)
         h = randn(g, B * T, 384, dtype=torch.bfloat16)
         wqkv = randn(g, 1152, 384, scale=0.05, dtype=torch.bfloat16)
-        assert fused.attention_qkv_supported(h, wqkv, T, H)
-        return lambda: (fused._attention_qkv_fwd(h, wqkv, B, T, H, 0.125, want_qkv=True, want_lse=True),
-                        fused._attention_qkv_fwd(h, wqkv, B, T, H, 0.125)[0])
+        assert attention.qkv_supported(h, wqkv, T, H)
+        return lambda: (attention.qkv_fwd(h, wqkv, B, T, H, 0.125, want_qkv=True, want_lse=True),
+                        attention.qkv_fwd(h, wqkv, B, T, H, 0.125)[0])
 
 
 # ------------------------------------------------------------------------------------------------------------------ row operations
@@ -1180,14 +1180,14 @@ def _():
 for _dt in DTYPES:
     @case("fused_attention_wrappers-%s" % DT[_dt])
     def _(dt=_dt):
-        from gm3d_amd import fused
+        from gm3d_amd import attention
         B, T, H = 2, 25, 6
         g = gen(25)
         qkv, dout = randn(g, B * T, 3 * H * 64, scale=1.5, dtype=dt), randn(g, B * T, H * 64, dtype=dt)
 
         def run():
-            out, lse = fused._attention_fwd(qkv, B, T, H, 0.125)
-            return out, lse, fused._attention_bwd(qkv, out, dout, lse, B, T, H, 0.125)
+            out, lse = attention.fwd(qkv, None, B, T, H, 64, 0.125, head=True, pad=True)
+            return out, lse, attention.bwd(qkv, None, out, dout, lse, B, T, H, 64, 0.125, head=True, pad=True)
         return run
 
     for _scaled in (True, False):

@@ -9,7 +9,7 @@ rows), gemm.wgrad_supported (no ldy >= N, ldx >= K), heads.group_max_supported (
 Stricter than the guard, kept: gemm.supported / ragged_supported / dma_supported / wgrad_supported require 16-byte aligned operands
 (the TN guard does not); gemm.supported requires N % 128 and K % 64 where the guard also takes the ragged form; ws_supported /
 pool16_supported / ws_bn_supported require M >= 32768 (a speed choice); heads.patch_chamfer_loss_supported requires pred rows
-of exactly 96 contiguous values.  Equal: heads.layer_norm_supported, heads.bn_bcast_supported, fused.attention_qkv_supported.
+of exactly 96 contiguous values.  Equal: heads.layer_norm_supported, heads.bn_bcast_supported, attention.qkv_supported.
 """
 from types import SimpleNamespace
 

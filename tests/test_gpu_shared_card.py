@@ -53,7 +53,7 @@ def _replays_equal(seg, opt, n):
 
 
 def test_replays_identical_beside_a_second_stream_of_this_process():
-    from gm3d_amd import fused, ops
+    from gm3d_amd import attention, ops
     seg, opt, data = _segmented_step(64)
     side = torch.cuda.Stream()
     big = torch.randn(4096, 4096, device="cuda", dtype=torch.bfloat16)
@@ -69,7 +69,7 @@ def test_replays_identical_beside_a_second_stream_of_this_process():
                 for _ in range(10):
                     (big @ big).relu_()
                     ops.fps(xyz, 64)
-                    fused._attention_qkv_fwd(h, wqkv, 64, 64, 6, 0.125)
+                    attention.qkv_fwd(h, wqkv, 64, 64, 6, 0.125)
                 side.synchronize()
 
     th = threading.Thread(target=busy)

@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 torch.cuda.set_device(0)
-from gm3d_amd import fused, gemm, ops
+from gm3d_amd import attention, fused, gemm, ops
 from tests import clouds
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 B, T, C, H = 128, 64, 384, 6
@@ -28,7 +28,7 @@ cases = {
     "knn_group k=32": lambda: ops.knn_group(data, cen, 32, return_idx=True),
     "residual_ln_fwd first (x+pos)": lambda: fused.residual_ln_fwd(None, x16, None, None, T, pos16, lnw, lnb, 1e-6, bf, R),
     "residual_ln_fwd mid (res+y+b)": lambda: fused.residual_ln_fwd(res32, x16, bproj, None, T, None, lnw, lnb, 1e-6, bf, R),
-    "attention_qkv_fwd": lambda: fused._attention_qkv_fwd(h16, wqkv, B, T, H, 0.125)[0],
+    "attention_qkv_fwd": lambda: attention.qkv_fwd(h16, wqkv, B, T, H, 0.125)[0],
     "mm proj 384->384": lambda: gemm.mm(h16, wproj),
     "mm fc2 1536->384": lambda: gemm.mm(g16, w2),
     "mm qkv 384->1152": lambda: gemm.mm(h16, wqkv),
@@ -55,7 +55,7 @@ if os.environ.get("LOAD") == "thread":
                 for _ in range(20):
                     (a @ a).relu_()
                     ops.fps(data, 64)
-                    fused._attention_qkv_fwd(h16, wqkv, B, T, H, 0.125)
+                    attention.qkv_fwd(h16, wqkv, B, T, H, 0.125)
                 side.synchronize()
     th = threading.Thread(target=busy)
     th.start()
