@@ -128,6 +128,13 @@ __device__ __forceinline__ void store_tile_t(unsigned char* img, int row0, const
 
 // The attention proper on the three LDS images, by wave w = query tile w of NT.  Oi: image whose rows 32 w .. 32 w + 31 this wave
 // may overwrite to stage its output rows (the Q image itself when nobody else reads those rows afterwards).
+//
+// A logit is the ROUNDED product s * scale everywhere in this file: the forward takes the row maximum of the rounded product and saves
+// lse = m + log(sum), so `s * scale - m` and the backward's `s * scale - lse` must not become one fma (contract(off) on the loops that
+// form them, and on nothing else).  Where scale is no power of two the fused form has the unrounded product: the largest logit gives
+// exp(+-1e-7) instead of exp(0) = 1, and the backward's P is not the forward's -- a head of ONE token returned dV != dO
+// (tests/test_gpu_attention_plain.py, the `scale` cases).  At a power of two (0.125: every model here) the product is exact and both
+// forms give the same bits.
 template <int NT>
 __device__ __forceinline__ void attn_core_bf16(const unsigned char* Qi, const unsigned char* Ki, const unsigned char* Vi,
                                                unsigned char* Oi, int w, int lane, int T, float scale, bf16_t* outp, size_t os,
@@ -149,6 +156,7 @@ __device__ __forceinline__ void attn_core_bf16(const unsigned char* Qi, const un
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
+#pragma clang fp contract(off)      // the logit is the ROUNDED s * scale: see the note above attn_core_bf16
             const int key = 32 * t + crow(g, hh);
             st[t][g] = key < T ? st[t][g] * scale : -INFINITY;
             m = fmaxf(m, st[t][g]);
@@ -159,6 +167,7 @@ __device__ __forceinline__ void attn_core_bf16(const unsigned char* Qi, const un
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
+#pragma clang fp contract(off)
             st[t][g] = __expf(st[t][g] - m);
             sum += st[t][g];
         }
@@ -370,6 +379,7 @@ __global__ __launch_bounds__(64 * MT) void attn_fwd_f32_kernel(const float* __re
     for (int t = 0; t < MT; ++t)
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
+#pragma clang fp contract(off)      // the logit is the ROUNDED s * scale: see the note above attn_core_bf16
             const int key = 32 * t + crow(g, hh);
             st[t][g] = key < T ? st[t][g] * scale : -INFINITY;
             m = fmaxf(m, st[t][g]);
@@ -380,6 +390,7 @@ __global__ __launch_bounds__(64 * MT) void attn_fwd_f32_kernel(const float* __re
     for (int t = 0; t < MT; ++t)
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
+#pragma clang fp contract(off)
             st[t][g] = expf(st[t][g] - m);
             sum += st[t][g];
         }
@@ -495,6 +506,7 @@ __global__ __launch_bounds__(128 * NT) void attn_bwd_bf16_kernel(const bf16_t* _
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
+#pragma clang fp contract(off)      // the forward's logit, bit for bit
                 const int q = 32 * qt + crow(g, hh);
                 const float p = (q < T && key < T) ? __expf(s[g] * scale - Ls[q]) : 0.f;
                 s[g] = p;                       // P[q][key]
@@ -526,6 +538,7 @@ __global__ __launch_bounds__(128 * NT) void attn_bwd_bf16_kernel(const bf16_t* _
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
+#pragma clang fp contract(off)
                 const int key = 32 * kt + crow(g, hh);
                 const float p = (q < T && key < T) ? __expf(s[g] * scale - lq) : 0.f;
                 dp[g] = p * (dp[g] - dq_);  // dS^T[key][q]
@@ -603,6 +616,7 @@ __global__ __launch_bounds__(128 * MT) void attn_bwd_f32_kernel(const float* __r
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
+#pragma clang fp contract(off)      // the forward's logit, bit for bit
                 const int q = 32 * qt + crow(g, hh);
                 const float p = (q < T && key < T) ? expf(s[g] * scale - Ls[q]) : 0.f;
                 s[g] = p;
@@ -642,6 +656,7 @@ __global__ __launch_bounds__(128 * MT) void attn_bwd_f32_kernel(const float* __r
             }
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
+#pragma clang fp contract(off)
                 const int key = 32 * kt + crow(g, hh);
                 const float p = (q < T && key < T) ? expf(s[g] * scale - lq) : 0.f;
                 dp[g] = p * (dp[g] - dq_) * scale;

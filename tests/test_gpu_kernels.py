@@ -142,6 +142,7 @@ def _attn_ref(qkv, H, scale):
 
 @pytest.mark.parametrize("T", [64, 25, 39, 1, 32, 33, 65, 96, 97, 128])
 def test_attention_f32(gops, T):
+    """Whole-tensor bars; the stricter check, per row and per (cloud, head) slice, is tests/test_gpu_attention_plain.py."""
     torch.manual_seed(T)
     B, H = 5, 6
     qkv = (torch.randn(B, T, 3 * H * 64, device="cuda") * 1.5).requires_grad_(True)
@@ -158,6 +159,7 @@ def test_attention_f32(gops, T):
 
 @pytest.mark.parametrize("T", [64, 25, 39, 65, 128])
 def test_attention_bf16(gops, T):
+    """Whole-tensor bars; the stricter check, per row and per (cloud, head) slice, is tests/test_gpu_attention_plain.py."""
     torch.manual_seed(100 + T)
     B, H = 4, 6
     qkv32 = torch.randn(B, T, 3 * H * 64, device="cuda")
@@ -281,7 +283,8 @@ def test_colsum_wide(R, C):
 def test_attention_beyond_128_tokens(gops, dtype, T):
     """ops.attention for 128 < T <= 512 (cfgs/config_3.yaml: 256 groups of 8; cls + 256 in fine-tuning): routed to the flash-style
     kernel of the hierarchical encoder with a NULL mask.  Forward and input gradient against an fp64 torch softmax attention;
-    fp32: 1e-5, bf16: one rounding of the operands and of the output (2e-2 / 3e-2 of the tensor scale)."""
+    fp32: 1e-5, bf16: one rounding of the operands and of the output (2e-2 / 3e-2 of the tensor scale).
+    The stricter check, per row and per (cloud, head) slice and at head_dim 16 and 32 too, is tests/test_gpu_attention_plain.py."""
     B, H, hd = 3, 6, 64
     if dtype == torch.bfloat16 and T > 256:
         # head_dim 64 in bf16: the backward keeps q, k, v, dO of the head in LDS (4 x T x 144 B): T <= 256; the C ABI says so
