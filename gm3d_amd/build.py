@@ -44,6 +44,7 @@ SOURCES = {
     "augment.hip": ["-ffp-contract=off"],
     "linprobe.hip": ["-ffp-contract=off"],
     "reconstruct.hip": ["-ffp-contract=off"],
+    "soft_ce.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

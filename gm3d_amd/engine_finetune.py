@@ -6,6 +6,11 @@ random subset of `npoints` of those indices shared by the batch (np.random.choic
 scale-and-translate augmentation, PointTransformer forward under bf16 autocast, cross-entropy, backward,
 gradient clipping, AdamW.  The reference runs fp16 autocast + GradScaler; bf16 needs no loss scaling, so the
 `loss_scaler` argument is accepted for signature compatibility and only its clip/step duty is performed.
+
+Soft targets (gm3d_amd/losses.py) are opt-in: build_criterion picks the smoothed loss a model's config or the driver's --smoothing asks
+for, and `mixup=PointMixup(alpha)` mixes the batch after train_transforms, where the reference's (commented) call stands
+(P/engine_finetune.py:136-137).  Host draws of one iteration, in this order: the FPS subset (np.random.choice), then the mixup's
+lam (rng.beta) and permutation (torch.randperm) -- the reference's.  With neither, every path issues the launches it always did.
 """
 import math
 import sys
@@ -90,6 +95,41 @@ def adjust_learning_rate(optimizer, epoch, args):
     return lr
 
 
+# --------------------------------------------------------------------------- the criterion
+def _model_smooth(model):
+    """The `smooth` of the model's config (Point-M2AE's fine-tune yamls), or 0."""
+    config = getattr(getattr(model, "module", model), "config", None)
+    if config is None:
+        return 0.0
+    v = config.get("smooth", 0.0) if isinstance(config, dict) else getattr(config, "smooth", 0.0)
+    return float(v or 0.0)
+
+
+def build_criterion(model=None, args=None):
+    """The switch of P/main_finetune.py:369-375 (commented out upstream), as an opt-in helper: SmoothLoss(smooth) when the model's
+    config sets `smooth` (Point-M2AE_SA3D/cfgs/finetune_modelnet_PointM2AE.yaml:73), else LabelSmoothingCrossEntropy(args.smoothing) when
+    that is positive, else nn.CrossEntropyLoss().  Mixup needs no criterion of its own: both smoothed losses take MixedTargets."""
+    from .losses import LabelSmoothingCrossEntropy, SmoothLoss
+    smooth = _model_smooth(model)
+    if smooth > 0.0:
+        return SmoothLoss(smooth)
+    smoothing = float(getattr(args, "smoothing", 0.0) or 0.0)
+    if smoothing > 0.0:
+        return LabelSmoothingCrossEntropy(smoothing)
+    return torch.nn.CrossEntropyLoss()
+
+
+def _check_mixup(mixup):
+    """None or a losses.PointMixup.  timm's image Mixup cannot mix point clouds (and upstream's call site for it names an undefined
+    variable), so anything else is refused rather than ignored."""
+    if mixup is None:
+        return None
+    from .losses import PointMixup
+    if not isinstance(mixup, PointMixup):
+        raise TypeError("mixup must be None or a gm3d_amd.losses.PointMixup, not %s" % type(mixup).__name__)
+    return mixup
+
+
 # --------------------------------------------------------------------------- the step
 def sample_points(points, npoints, subset=None, rng=np.random):
     """P/engine_finetune.py:117-134: FPS to point_all, keep a random `npoints`-subset of the FPS order (the same
@@ -107,13 +147,19 @@ def sample_points(points, npoints, subset=None, rng=np.random):
 
 
 def finetune_step(model, criterion, optimizer, points, targets, npoints=1024, max_norm=None, bf16=True, subset=None,
-                  aug_draws=None, augment=True, update=True, accum_iter=1, presampled=False):
+                  aug_draws=None, augment=True, update=True, accum_iter=1, presampled=False, mixup=None, mixup_drawn=False):
     """One iteration of P/engine_finetune.py:108-151.  points (B,N0,3) f32 and targets (B,) on the GPU.
     presampled=True: `points` already is the (B,npoints,3) output of sample_points (sampling overlapped elsewhere).
+    mixup: a losses.PointMixup applied after train_transforms -- its host draw (lam, permutation) is made here, after the subset's,
+    unless mixup_drawn (the caller staged it with mixup.draw: the captured step, parity tests); the criterion then receives
+    MixedTargets.  None: today's path, launch for launch.
     -> {'loss', 'grad_norm', 'outputs'} as device tensors (no host sync)."""
+    _check_mixup(mixup)
     pts = points if presampled else sample_points(points, npoints, subset=subset)
     if augment:
         pts = train_transforms(pts, draws=aug_draws)
+    if mixup is not None:
+        pts, targets = mixup.mix(pts, targets) if mixup_drawn else mixup(pts, targets)
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
         outputs = model(pts)
         loss = criterion(outputs.float(), targets.long())
@@ -144,11 +190,12 @@ class GraphedFinetuneStep:
     arithmetic and the same order of host random draws as the single-graph form."""
 
     def __init__(self, model, criterion, optimizer, example_points, example_targets, npoints=1024, max_norm=None, bf16=True,
-                 warmup_iters=3, rng=np.random, augment=True, overlap_sampling=False):
+                 warmup_iters=3, rng=np.random, augment=True, overlap_sampling=False, mixup=None):
         """The `warmup_iters` un-captured iterations are real optimisation steps on the example batch (the allocator and
         the optimizer state must be warm before capture): pass warmup_iters=0 when the optimizer state already exists."""
         self.model, self.criterion, self.opt = model, criterion, optimizer
         self.npoints, self.max_norm, self.bf16, self.rng, self.augment = npoints, max_norm, bf16, rng, augment
+        self.mixup, self._captured = _check_mixup(mixup), False
         self.point_all = min(POINT_ALL[npoints], example_points.size(1))
         self.points = example_points.clone()
         self.targets = example_targets.clone()
@@ -156,6 +203,7 @@ class GraphedFinetuneStep:
         self._feed = streams.PinnedFeed(self.subset)
         self.overlap = bool(overlap_sampling)
         self._draw()
+        self._draw_mixup()
         if self.overlap:
             self.pts = sample_points(self.points, npoints, subset=self.subset)
             self.staged = torch.zeros_like(self.pts)
@@ -165,6 +213,7 @@ class GraphedFinetuneStep:
         self.graph = torch.cuda.CUDAGraph()
         with streams.capture(self.graph):
             self.out = self._body()
+        self._captured = True
         if self.overlap:          # the sampler stream's graph: clouds + subset -> FPS + gather -> self.staged
             self.stage.capture(lambda: self.staged.copy_(sample_points(self.points, npoints, subset=self.subset)))
             torch.cuda.synchronize()
@@ -173,24 +222,39 @@ class GraphedFinetuneStep:
         """Host draw of the shared FPS subset -> device, on the current stream."""
         self._feed.push([self.rng.choice(self.point_all, self.npoints, False).astype(np.int64)])
 
+    def _draw_mixup(self):
+        """Host draw of the mixup (lam, then the permutation) -> its device tensors and, once captured, the criterion's coefficients
+        (before the capture the eager warm-up iterations stage them from the MixedTargets).  On the current stream, the replay's:
+        unlike the subset this is never drawn one batch ahead, so the sequence of host draws stays subset, mixup, subset, mixup."""
+        if self.mixup is None:
+            return
+        lam, _ = self.mixup.draw(self.points.size(0), self.points.device)
+        stage = getattr(self.criterion, "stage", None)
+        if self._captured and stage is not None:
+            stage(lam)
+
     def _body(self):
         if self.overlap:
             return finetune_step(self.model, self.criterion, self.opt, self.pts, self.targets, npoints=self.npoints,
-                                 max_norm=self.max_norm, bf16=self.bf16, augment=self.augment, presampled=True)
+                                 max_norm=self.max_norm, bf16=self.bf16, augment=self.augment, presampled=True, mixup=self.mixup,
+                                 mixup_drawn=True)
         return finetune_step(self.model, self.criterion, self.opt, self.points, self.targets, npoints=self.npoints,
-                             max_norm=self.max_norm, bf16=self.bf16, subset=self.subset, augment=self.augment)
+                             max_norm=self.max_norm, bf16=self.bf16, subset=self.subset, augment=self.augment, mixup=self.mixup,
+                             mixup_drawn=True)
 
     def __call__(self, points, targets, next_points=None):
         if not self.overlap:
             self.points.copy_(points, non_blocking=True)
             self.targets.copy_(targets, non_blocking=True)
             self._draw()
+            self._draw_mixup()
             self.graph.replay()
             return self.out
         # the subset is drawn on the sampler stream, between the clouds' copy and the sampling graph that reads it
         self.stage.take(points, self.points, before_replay=self._draw)
         self.pts.copy_(self.staged)
         self.targets.copy_(targets, non_blocking=True)
+        self._draw_mixup()
         if next_points is not None:               # queued BEFORE the training graph so that the two run side by side
             self.stage.enqueue(next_points, self.points, before_replay=self._draw)
         self.graph.replay()
@@ -203,7 +267,14 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     (the reference syncs on loss.item() every iteration; a non-finite loss still stops the run at the next read).
     step: a GraphedFinetuneStep built on this model / optimizer -- the iteration is then a graph replay, and with
     overlap_sampling the loader is read one batch ahead so that the next batch's point sampling runs beside the current
-    batch's training graph (accum_iter must be 1; a last batch of a different size runs eagerly)."""
+    batch's training graph (accum_iter must be 1; a last batch of a different size runs eagerly).
+    mixup_fn: None or a losses.PointMixup (TypeError otherwise), applied after train_transforms; with `step` it is the one the step
+    was built with (a different one is a ValueError)."""
+    _check_mixup(mixup_fn)
+    step_mixup = getattr(step, "mixup", None)
+    if mixup_fn is not None and step is not None and step_mixup is not mixup_fn:
+        raise ValueError("mixup_fn must be the PointMixup the GraphedFinetuneStep was built with")
+    mixup_fn = step_mixup if mixup_fn is None else mixup_fn
     model.train(True)
     accum_iter = getattr(args, "accum_iter", 1)
     if step is not None and accum_iter != 1:
@@ -226,7 +297,7 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         else:
             out = finetune_step(model, criterion, optimizer, points, targets, npoints=npoints,
                                 max_norm=max_norm if max_norm else None, bf16=getattr(args, "bf16", True),
-                                update=(it + 1) % accum_iter == 0, accum_iter=accum_iter)
+                                update=(it + 1) % accum_iter == 0, accum_iter=accum_iter, mixup=mixup_fn)
         last = out["loss"]
         if (it + 1) % print_freq == 0 or it + 1 == n_iter:
             v = float(last)

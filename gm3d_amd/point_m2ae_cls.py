@@ -16,6 +16,13 @@ Linear(256,256) BN ReLU Dropout(0.5) Linear(256,cls) with F = 384 (ModelNet40, 4
     cat([x.mean(1), x.max(1)[0]], -1);
   * the max-pool's gradient goes to the lowest token index among tied maxima.
 
+What of the yaml's `model` section is read: NAME, group_sizes, num_groups, encoder_depths, encoder_dims, local_radius, drop_path_rate,
+num_heads, cls_dim and `smooth` (finetune_modelnet_PointM2AE.yaml:73 sets 0.3; the ScanObjectNN yamls set none).  A non-zero `smooth`
+makes the model's own loss (loss_ce, get_loss_acc) losses.SmoothLoss(smooth) -- Point-M2AE's smoothed cross-entropy, on-value
+1 - smooth, off-value smooth / (cls_dim - 1) --; absent or 0 it is nn.CrossEntropyLoss().  The fine-tune engine takes its criterion
+from the caller: engine_finetune.build_criterion(model) hands out the loss this config asks for.  Nothing else of the yaml (optimizer,
+scheduler, dataset, batch size, clipping) is read here; the engine's arguments carry those.
+
 GPU: the tail (pooling, head, both training-mode BatchNorms with their running statistics, Dropout) is ops.cls_tail -- two launches
 forward, two backward (gm3d_amd/csrc/cls_tail.hip); the Dropout factors come from one graph-safe device draw.  FUSED_TAIL = False
 runs the same tail as PyTorch modules (the CPU path and the cross-check).
@@ -87,7 +94,17 @@ class PointM2AEClassifier(nn.Module):
             nn.Linear(feat, 256), nn.BatchNorm1d(256), nn.ReLU(inplace=True), nn.Dropout(0.5),
             nn.Linear(256, 256), nn.BatchNorm1d(256), nn.ReLU(inplace=True), nn.Dropout(0.5),
             nn.Linear(256, self.cls_dim))
-        self.loss_ce = nn.CrossEntropyLoss()
+        has = "smooth" in config if isinstance(config, dict) else hasattr(config, "smooth")
+        self.smooth = float(_cfg(config, "smooth") or 0.0) if has else 0.0
+        self.build_loss_func()
+
+    def build_loss_func(self):
+        """nn.CrossEntropyLoss(), or losses.SmoothLoss(smooth) when the config sets a non-zero `smooth`."""
+        if self.smooth:
+            from .losses import SmoothLoss
+            self.loss_ce = SmoothLoss(self.smooth)
+        else:
+            self.loss_ce = nn.CrossEntropyLoss()
 
     def get_loss_acc(self, ret, gt):
         loss = self.loss_ce(ret, gt.long())

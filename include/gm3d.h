@@ -966,6 +966,41 @@ int gm3d_reconstruct_partition(const void *pred, const float *neighborhood, cons
                                int G, int k, int dtype, float *dense, float *full_center, int *order, int *n_visible,
                                gm3d_stream_t stream);
 
+/* ---- Soft-target cross-entropy and point mixup (gm3d_amd/csrc/soft_ce.hip, gm3d_amd/losses.py) -----------------------------------------
+ * gm3d_soft_ce_fwd: logits (B,C) f32 or bf16 (dtype), all arithmetic f32.  The target row t_i is given in exactly one of two forms:
+ *   compact: ya (B) int64, yb (B) int64 or NULL, coef (3) f32 ON THE DEVICE = (wa, wb, u): t_ic = u + wa [c = ya_i] + wb [c = yb_i]
+ *            (with yb NULL the wb term is absent and coef[1] is not used);
+ *   dense:   dense (B,C) f32 (ya, yb and coef NULL).
+ * Per row: m = max_c z_c, lse_i = m + log sum_c exp(z_c - m), row_loss_i = sum_c t_ic (lse_i - z_c) formed as written -- products of a
+ * weight and the non-negative lse - z_c; compact: (wa (lse - z[ya]) + wb (lse - z[yb])) + u sum_c (lse - z_c), the last term left out
+ * when u == 0.  loss (1) = the mean of row_loss over B.  A label outside [0, C) makes that row's loss (and the mean) NaN, as in
+ * gm3d_cls_tail_fwd; its lse is still written.  row_loss (B), lse (B) and loss (1) f32 are all written.  One launch of one workgroup
+ * (one wave per row, min(16, B) waves); the sums run in the fixed order soft_ce.hip states, without atomics.
+ *
+ * gm3d_soft_ce_bwd: dlogits_ic = dloss[0] / B * (S_i exp(z_c - lse_i) - t_ic) in the logits' dtype, S_i = sum_c t_ic (compact:
+ * (C u + wa) + wb; dense: summed, nothing assumed), from the same target arguments, the forward's lse (B) and dloss (1) f32.
+ * exp(z_c - lse_i) is divided by its own row sum, which is 1 up to the rounding of the stored lse_i (half an ulp of lse: 1.5e-5 at
+ * |lse| = 300) and takes that rounding out again.  A row whose label is outside [0, C) is NaN.  One launch, one wave per row, every
+ * element written once by its one owner.
+ *
+ * Limits, checked on the host before any launch: GM3D_EINVAL for a NULL logits or output, B < 0, C < 1, an unknown dtype, both target
+ * forms or neither, a compact form without ya or coef; GM3D_EUNSUPPORTED for B > 4096 or C > 1024.  B == 0 returns GM3D_OK after the
+ * checks without a launch.
+ *
+ * gm3d_mixup_points (Point-MAE_SA3D/engine_finetune.py:43-76): out[b] = fl(fl(l x[b]) + fl(m x[perm[b]])) for x (B,N,3) f32 -- two
+ * products rounded separately and one add, no FMA -- with coef2 (2) f32 ON THE DEVICE = (l, m) = (f32(lam), f32(1 - lam)), perm (B)
+ * int64 on the device; the same launch writes yb[b] = ya[perm[b]] (ya, yb (B) int64: both or neither).  Out of place (a cloud is read by
+ * two outputs): out == x is refused.  perm cannot be checked on the host; values in [0, B) are the caller's contract, and one outside
+ * reads nothing: that cloud becomes NaN and its yb -1.  One workgroup per cloud, one launch.
+ * Limits as gm3d_augment's: GM3D_EINVAL for a NULL x / perm / coef2 / out, out == x, N < 1, B < 0, ya without yb or yb without ya; no
+ * limit on N.  B == 0 returns GM3D_OK without a launch. */
+int gm3d_soft_ce_fwd(const void *logits, int B, int C, const long long *ya, const long long *yb, const float *coef, const float *dense,
+                     float *row_loss, float *lse, float *loss, int dtype, gm3d_stream_t stream);
+int gm3d_soft_ce_bwd(const void *logits, int B, int C, const long long *ya, const long long *yb, const float *coef, const float *dense,
+                     const float *lse, const float *dloss, void *dlogits, int dtype, gm3d_stream_t stream);
+int gm3d_mixup_points(const float *x, int B, int N, const long long *perm, const float *coef2, const long long *ya, float *out,
+                      long long *yb, gm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
