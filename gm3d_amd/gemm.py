@@ -519,7 +519,8 @@ def route_pool(x, w, group_rows):
 def linear_pool(x, w, bias, bias_after_pool, want_rows, group_rows=32, route=None):
     """Conv1d(k=1) over (groups*group_rows, K) rows + max over each group's rows in the GEMM epilogue, on what `route_pool` names
     (route: its answer, when the caller has asked already).
-    -> (rows (M,N) bf16 | None, pooled (M/group_rows,N) bf16, argmax (M/group_rows,N) uint8)."""
+    -> (rows (M,N) bf16 | None: the values that were pooled -- with the bias, without it when bias_after_pool --,
+    pooled (M/group_rows,N) bf16, argmax (M/group_rows,N) uint8: the first maximising row)."""
     kind, args = route or route_pool(x, w, group_rows)
     if kind == "split":
         raise ValueError("no kernel carries the pool epilogue for this product: run it split (route_pool)")

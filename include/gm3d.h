@@ -423,7 +423,9 @@ int gm3d_gemm_tn_bf16_gelu(const void *A, const void *W, const float *bias, void
  * rows are (group, point) with 32 points per group (M % 32 == 0).  P (M/32,N) bf16 = max_k, arg (M/32,N) u8 = its first argmax.
  * bias_after_pool = 0: C (optional) = A.W^T + bias is written and pooled (conv2: the rows feed the next layer);
  * bias_after_pool = 1: the product is pooled and the bias added to the maximum (conv4: C may be NULL -- the (M,N) product is
- * never needed again, not even by the backward, which works from `arg`). */
+ * never needed again, not even by the backward, which works from `arg`); C, when given, is the product that was pooled, WITHOUT the
+ * bias, on every kernel that carries this epilogue.  Ties go to the first row, as in gm3d_group_max_fwd (the values are compared
+ * as the bf16 numbers C holds; -0 == +0). */
 int gm3d_gemm_tn_bf16_pool(const void *A, const void *W, const float *bias, void *C, void *P, uint8_t *arg, int M, int N, int K,
                            int lda, int ldw, int ldc, int ldp, int bias_after_pool, gm3d_stream_t stream);
 /* fc2 input gradient + GELU backward in the GEMM epilogue (timm Mlp backward): dF (M,N) bf16 = (dO (M,K) . Wt (N,K)^T) *

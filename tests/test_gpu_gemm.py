@@ -1,5 +1,7 @@
 """-m gpu: the hand-written bf16 MFMA GEMM (gm3d_gemm_tn_bf16) against an fp32 matmul of the same bf16 operands.
-Tolerance: one bf16 rounding of the result (2^-8 relative) plus fp32 accumulation-order noise."""
+Tolerance: one bf16 rounding of the result (2^-8 relative) plus fp32 accumulation-order noise.
+These are whole-tensor bars and kernel-against-kernel equalities at the step's sizes; the stricter check, every kernel per element
+against fp64 on graded, cancelling and exact inputs and behind NaN fences, is tests/test_gpu_gemm_bf16_fp64.py."""
 import pytest
 import torch
 
