@@ -14,6 +14,12 @@
 // (csrc/attention.hip) this shape ran the 4096 x 1152 x 384 product in about 6.5 us against 11.3 (library) / 12.4 (gemm.hip).
 // Accumulation order is that of gemm.hip / gemm_ring.hip (k ascending in steps of 16 inside 32x32x16 MFMAs): identical bits.
 //
+// Where a workgroup's time goes (tools/gelu_dma_probe.py, profiles/gelu_dma_phases.txt; 4096 x 1536 x 384, 64-row tiles): K-loop
+// 4.7 us of 10.5, and the two workgroups of a CU together already pull 80-90 GB/s from L2 in it, the most a CU gets: a deeper
+// ring of half-stages made it SLOWER (profiles/NEGATIVE_RESULTS.md).  The other half is the epilogue, bound by the VALU work of the
+// GELU (about 26 instructions per element, 33 for GELU'), on top of which every pass of its store loop used to wait for its own
+// bias (and Fpre) loads.  Those loads are now requested once, before the last K-stage is multiplied (comment in the kernel).
+//
 // Round 3: the tile WIDTH is a template parameter (NJ 32-column MFMA tiles per wave: 128 / 192 / 256 columns).  The 256-wide form
 // serves the mini-PointNet convolutions over the 262,144 point rows (Encoder.second_conv, P/models_mae_learn_loss.py:878-883, and
 // their input gradients: N = 512 / 256), which are HBM-bound products (A read once + C written once = 400 MB at N = 512): a
@@ -81,27 +87,61 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_dma_kernel(const bf16_t* __res
 #pragma unroll
             for (int g = 0; g < 16; ++g) acc[i][j][g] = 0.f;
 
+#define GM3D_DMA_MULT(ST)                                                                           \
+    {                                                                                               \
+        const unsigned char* as = dsm + ((ST) & 1) * STAGE;                                         \
+        const unsigned char* ws = as + BM * 128;                                                    \
+        _Pragma("unroll") for (int s = 0; s < 4; ++s) {                                             \
+            bf16x8 fa[WMI];                                                                         \
+            _Pragma("unroll") for (int i = 0; i < WMI; ++i)                                         \
+                fa[i] = *reinterpret_cast<const bf16x8*>(as + swz_off(wm + 32 * i + r, 2 * s + hh)); \
+            _Pragma("unroll") for (int j = 0; j < NJ; ++j) {                                        \
+                const bf16x8 fw = *reinterpret_cast<const bf16x8*>(ws + swz_off(wn + 32 * j + r, 2 * s + hh)); \
+                _Pragma("unroll") for (int i = 0; i < WMI; ++i) acc[i][j] = mfma_bf16(fw, fa[i], acc[i][j]); \
+            }                                                                                       \
+        }                                                                                           \
+    }
     const int KT = K / DBK;
     GM3D_DMA_STAGE(0)
-    for (int kt = 0; kt < KT; ++kt) {
+    for (int kt = 0; kt + 1 < KT; ++kt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this wave's pieces of stage kt have landed ...
         __builtin_amdgcn_s_barrier();                             // ... everybody's have, and nobody still reads the other buffer
-        if (kt + 1 < KT) GM3D_DMA_STAGE(kt + 1)
-        const unsigned char* as = dsm + (kt & 1) * STAGE;
-        const unsigned char* ws = as + BM * 128;
+        GM3D_DMA_STAGE(kt + 1)
+        GM3D_DMA_MULT(kt)
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the last stage: none of this wave's loads is out behind it
+    __builtin_amdgcn_s_barrier();
+    // The epilogue's global operands -- the bias, and the Fpre tile of the GELU backward, written a whole forward pass earlier (a
+    // cold HBM round trip) -- are requested HERE, before the last stage is multiplied, and held in registers (Fpre: 24 / 48 VGPRs)
+    // while the tile is staged, instead of after the K-loop and two barriers.  Behind the last counted wait and not earlier: VMEM
+    // loads return in order, so an older cold load would hold back the count of every stage requested after it.  Same addresses
+    // and values as the loads they replace (Fpre rows past M clamped like the A rows: no branch, never used).  The 256-column
+    // tile keeps its bias loads in the staging loop (registers).
+    constexpr bool BIAS_ACC = NJ < 4;
+    float bv[NJ][8];                                              // (what an instance does not fill is never read)
+    float4 bq[NJ][4];
+    uint4 fraw[2 * NJ * WMI];
+    const bool bias_first = (EPI == 0 || (EPI == 3 && !bias_after_pool)) && bias;
+    if (EPI == 1 || EPI == 2) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            bf16x8 fa[WMI];
+        for (int t = 0; t < NJ; ++t) V8<float>::load(bias + n0 + 64 * t + 8 * (tid & 7), bv[t]);
+    } else if (BIAS_ACC && bias_first) {
 #pragma unroll
-            for (int i = 0; i < WMI; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(as + swz_off(wm + 32 * i + r, 2 * s + hh));
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const bf16x8 fw = *reinterpret_cast<const bf16x8*>(ws + swz_off(wn + 32 * j + r, 2 * s + hh));
+            for (int q = 0; q < 4; ++q) bq[j][q] = *reinterpret_cast<const float4*>(bias + n0 + wn + 32 * j + 8 * q + 4 * hh);
+    }
+    if (EPI == 2) {
 #pragma unroll
-                for (int i = 0; i < WMI; ++i) acc[i][j] = mfma_bf16(fw, fa[i], acc[i][j]);
-            }
+        for (int i = 0; i < 2 * NJ * WMI; ++i) {                  // the chunks of the store loop below, same index arithmetic
+            const int c = tid + 256 * i;
+            const int t = i / (2 * WMI), row = (c - t * (BM * 8)) >> 3;
+            const int fm = m0 + row < M ? m0 + row : M - 1;
+            fraw[i] = *reinterpret_cast<const uint4*>(Fpre + (size_t)fm * ldfp + n0 + 64 * t + 8 * (tid & 7));
         }
     }
+    GM3D_DMA_MULT(KT - 1)
+#undef GM3D_DMA_MULT
 #undef GM3D_DMA_STAGE
     __syncthreads();                 // every wave is done with the stages: they become the bf16 staging images of the epilogue
     // acc[i][j][g]: row wm + 32 i + r, column wn + 32 j + crow(g) (4 consecutive per quad: 8 q + 4 hh + e).  Staged as NJ
@@ -116,8 +156,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_dma_kernel(const bf16_t* __res
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float v[4] = {acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]};
-                if ((EPI == 0 || (EPI == 3 && !bias_after_pool)) && bias) {
-                    const float4 b = *reinterpret_cast<const float4*>(bias + n0 + col + 8 * q + 4 * hh);
+                if (bias_first) {
+                    const float4 b = BIAS_ACC ? bq[j][q] : *reinterpret_cast<const float4*>(bias + n0 + col + 8 * q + 4 * hh);
                     v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
                 }
                 bf16x4 pk;
@@ -182,19 +222,17 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_dma_kernel(const bf16_t* __res
                 *reinterpret_cast<uint4*>(C + (size_t)(m0 + row) * ldc + n) = raw;
             } else {
                 const bf16x8 f = *reinterpret_cast<const bf16x8*>(&raw);
-                float bv[8], v[8];
-                V8<float>::load(bias + n, bv);
+                float v[8];
                 if (EPI == 1) {
                     if (C) *reinterpret_cast<uint4*>(C + (size_t)(m0 + row) * ldc + n) = raw;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = gelu_f<bf16_t>((float)f[e] + bv[e]);
+                    for (int e = 0; e < 8; ++e) v[e] = gelu_f<bf16_t>((float)f[e] + bv[t][e]);
                     V8<bf16_t>::store(G + (size_t)(m0 + row) * ldg + n, v);
                 } else {
-                    float fv[8];
-                    V8<bf16_t>::load(Fpre + (size_t)(m0 + row) * ldfp + n, fv);
+                    const bf16x8 fp = *reinterpret_cast<const bf16x8*>(&fraw[i]);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        v[e] = (float)f[e] * gelu_grad_f<bf16_t>(fv[e] + bv[e]);
+                        v[e] = (float)f[e] * gelu_grad_f<bf16_t>((float)fp[e] + bv[t][e]);
                         csum[t][e] += v[e];
                     }
                     V8<bf16_t>::store(C + (size_t)(m0 + row) * ldc + n, v);
