@@ -341,6 +341,111 @@ __global__ __launch_bounds__(256) void chamfer_small_bwd_kernel(const float* __r
     }
 }
 
+// ---- the fused masked-patch loss for patches of K = 8 / 16 points (128 x 16 and 256 x 8 pre-training) -----------------------------
+// patch_loss_fwd_kernel / patch_loss_bwd_kernel above with the layout of chamfer_small_*: a patch on a SEGMENT of K lanes, 64 / K
+// patches per wave, 256 / K per workgroup; lane l of a segment holds predicted point l (read from `pred` as it lies, any float type,
+// batch-strided) AND true point l (gathered through `ids`).  Chosen over 2K lanes per patch (one cloud per half, as the 32-point
+// kernel lays it out) because only `pred` has a gradient: with both points in one lane the backward needs the direction-2 terms of
+// the segment and nothing else, no lane computes a sum that is thrown away and no half of the wave idles at the store; the forward
+// costs the same shuffles per patch either way.  Partners are reached by __shfl(v, t, K) (ds_bpermute, the source lane is the
+// segment's base + t): the 32-point kernel's v_readlane needs ONE lane number for the whole wave, here it differs per segment, and
+// a DPP row move reaches fixed offsets only, not the data-dependent argmin lane of the backward.
+// Arithmetic as the 32-point kernels: sqdist3 (no FMA), j == 0 seeds, strict <, ascending j.  Sums, in this order:
+//   forward   s_l = d1[l] + d2[l] in lane l (L1: sqrt d1[l] + sqrt d2[l]), then the xor tree s += s[l ^ w] for w = K/2, K/4 .. 1 inside
+//             the segment; matrix[p] = s / K (L1: s / 2K), exact scalings; mean_small_kernel finishes the scalar as for 32 points;
+//   backward  acc = this point's own term 2 (a_l - b[k1_l]) g, then for j = 0 .. K-1 ascending: acc -= 2 (b_j - a[k2_j]) g_j where
+//             k2_j == l -- the order of chamfer32_bwd_kernel and chamfer_small_bwd_kernel.
+// No LDS, no atomics, no zero fill.  Segments past the last patch (and, in the backward, those of the `lead` zero rows) clamp their
+// patch index, take part in every shuffle and write nothing (zeros for the lead rows).
+template <int K, class T, bool L1>
+__global__ __launch_bounds__(256) void patch_loss_small_fwd_kernel(const T* __restrict__ pred, size_t pred_bstride,
+                                                                   const float* __restrict__ target, const long long* __restrict__ ids,
+                                                                   size_t ids_bstride, int B, int Tn, int M, float* __restrict__ matrix,
+                                                                   int32_t* __restrict__ i1, int32_t* __restrict__ i2) {
+    const int seg = blockIdx.x * (256 / K) + threadIdx.x / K, l = threadIdx.x % K;
+    const bool live = seg < B * M;
+    const int p = live ? seg : 0;
+    const int b = p / M, m = p - b * M;
+    const T* pp = pred + (size_t)b * pred_bstride + (size_t)m * (3 * K) + l * 3;
+    const float ax = (float)pp[0], ay = (float)pp[1], az = (float)pp[2];
+    const long long id = ids[(size_t)b * ids_bstride + m];
+    const float* tp = target + (((size_t)b * Tn + (size_t)id) * K + l) * 3;
+    const float bx = tp[0], by = tp[1], bz = tp[2];
+    float best1 = 0.f, best2 = 0.f;
+    int k1 = 0, k2 = 0;
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+        const float tbx = __shfl(bx, t, K), tby = __shfl(by, t, K), tbz = __shfl(bz, t, K);
+        const float tax = __shfl(ax, t, K), tay = __shfl(ay, t, K), taz = __shfl(az, t, K);
+        const float e1 = sqdist3(ax, ay, az, tbx, tby, tbz), e2 = sqdist3(bx, by, bz, tax, tay, taz);
+        if (t == 0 || e1 < best1) { best1 = e1; k1 = t; }
+        if (t == 0 || e2 < best2) { best2 = e2; k2 = t; }
+    }
+    if (live) {
+        const size_t o = (size_t)p * K + l;
+        i1[o] = k1; i2[o] = k2;
+    }
+    if constexpr (L1) { best1 = sqrtf(best1); best2 = sqrtf(best2); }
+    float s = __fadd_rn(best1, best2);
+#pragma unroll
+    for (int w = K / 2; w > 0; w >>= 1) s = __fadd_rn(s, __shfl_xor(s, w, K));
+    if (live && l == 0) matrix[p] = s * (L1 ? 0.5f / (float)K : 1.0f / (float)K);
+}
+
+template <int K, class T, bool L1>
+__global__ __launch_bounds__(256) void patch_loss_small_bwd_kernel(const T* __restrict__ pred, size_t pred_bstride,
+                                                                   const float* __restrict__ target, const long long* __restrict__ ids,
+                                                                   size_t ids_bstride, const int32_t* __restrict__ i1,
+                                                                   const int32_t* __restrict__ i2, const float* __restrict__ gmean, int B,
+                                                                   int Tn, int M, T* __restrict__ dpred, int lead) {
+    // lead > 0: dpred is the gradient of the FULL (B, lead + M, 3K) prediction; the first `lead` patches of every cloud get zeros
+    const int seg = blockIdx.x * (256 / K) + threadIdx.x / K, l = threadIdx.x % K;
+    const int LM = lead + M;
+    const bool live = seg < B * LM;
+    const int q = live ? seg : 0;
+    const int b = q / LM, mm = q - b * LM - lead;
+    const bool zero = mm < 0;
+    const int m = zero ? 0 : mm;
+    const size_t o = ((size_t)b * M + m) * K + l;
+    const T* pp = pred + (size_t)b * pred_bstride + (size_t)m * (3 * K) + l * 3;
+    const float a[3] = {(float)pp[0], (float)pp[1], (float)pp[2]};
+    const long long id = ids[(size_t)b * ids_bstride + m];
+    const float* tp = target + (((size_t)b * Tn + (size_t)id) * K + l) * 3;
+    const float bt[3] = {tp[0], tp[1], tp[2]};
+    const int k1 = i1[o], k2 = i2[o];
+    float ob[3], oa[3];                     // this point's neighbours: the true point k1 and the predicted point k2
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { ob[d] = __shfl(bt[d], k1, K); oa[d] = __shfl(a[d], k2, K); }
+    // d mean / d (d1 | d2)[point] = (g / (B M)) / K: the two divisions autograd makes for mean() of mean(dim=-1)
+    float g1 = (gmean[0] / (float)(B * M)) / (float)K, g2 = g1;
+    if constexpr (L1) {
+        // autograd's chain for (mean(sqrt d1) + mean(sqrt d2)) / 2: g / 2, / (B M K), / (2 sqrt d); d recomputed as the forward formed it
+        const float h = (gmean[0] / 2.0f) / (float)(B * M * K);
+        g1 = h / (2.0f * sqrtf(sqdist3(a[0], a[1], a[2], ob[0], ob[1], ob[2])));
+        g2 = h / (2.0f * sqrtf(sqdist3(bt[0], bt[1], bt[2], oa[0], oa[1], oa[2])));
+    }
+    float acc[3], t2[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        acc[d] = __fmul_rn(__fmul_rn(2.0f, __fsub_rn(a[d], ob[d])), g1);
+        t2[d] = __fmul_rn(__fmul_rn(2.0f, __fsub_rn(bt[d], oa[d])), g2);
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const bool hit = __shfl(k2, j, K) == l;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const float v = __shfl(t2[d], j, K);
+            if (hit) acc[d] = __fsub_rn(acc[d], v);
+        }
+    }
+    if (live) {
+        T* out = dpred + (size_t)q * (3 * K) + l * 3;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) out[d] = (T)(zero ? 0.f : acc[d]);
+    }
+}
+
 }  // namespace gm3d
 
 extern "C" int gm3d_chamfer_fwd(const float* xyz1, const float* xyz2, int P, int n, int m, float* dist1,
@@ -463,5 +568,67 @@ extern "C" int gm3d_patch_chamfer_l1_loss_bwd(const void* pred, long long pred_b
         using E = std::remove_pointer_t<decltype(t)>;
         return launch_lds<patch_loss_bwd_kernel<E, true>>(dim3((P + 3) / 4), dim3(256), 0, stream, (const E*)pred, (size_t)pred_bstride,
                                                           target, ids, (size_t)ids_bstride, idx1, idx2, gmean, B, T, M, (E*)dpred, 0);
+    });
+}
+
+extern "C" int gm3d_patch_chamfer_loss_k_fwd(const void* pred, long long pred_bstride, const float* target, const long long* ids,
+                                             long long ids_bstride, int B, int T, int M, int k, int l1, float* matrix, int32_t* idx1,
+                                             int32_t* idx2, float* mean_out, int dtype, gm3d_stream_t stream) {
+    using namespace gm3d;
+    if (!pred || !target || !ids || !matrix || !idx1 || !idx2 || !mean_out || B < 0 || T < 1 || M < 1 || M > T) return GM3D_EINVAL;
+    if (k != 8 && k != 16 && k != 32) return GM3D_EUNSUPPORTED;
+    if (pred_bstride < (long long)M * 3 * k || ids_bstride < M) return GM3D_EINVAL;
+    if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
+    if ((long long)B * M * k > 0x7fffffffLL) return GM3D_EUNSUPPORTED;      // B * M * k is formed in int
+    if (B == 0) return GM3D_OK;
+    if (k == 32)
+        return (l1 ? gm3d_patch_chamfer_l1_loss_fwd : gm3d_patch_chamfer_loss_fwd)(pred, pred_bstride, target, ids, ids_bstride, B, T, M,
+                                                                                  matrix, idx1, idx2, mean_out, dtype, stream);
+    const int P = B * M;
+    const int rc = by_int<8, 16>(k, [&](auto c) {
+        constexpr int K = decltype(c)::value, PPB = 256 / K;
+        return by_dtype(dtype, [&](auto* t) {
+            using E = std::remove_pointer_t<decltype(t)>;
+            const dim3 grid((P + PPB - 1) / PPB), block(256);
+            if (l1)
+                return launch_lds<patch_loss_small_fwd_kernel<K, E, true>>(grid, block, 0, stream, (const E*)pred, (size_t)pred_bstride,
+                                                                          target, ids, (size_t)ids_bstride, B, T, M, matrix, idx1, idx2);
+            return launch_lds<patch_loss_small_fwd_kernel<K, E, false>>(grid, block, 0, stream, (const E*)pred, (size_t)pred_bstride,
+                                                                       target, ids, (size_t)ids_bstride, B, T, M, matrix, idx1, idx2);
+        });
+    });
+    if (rc != GM3D_OK) return rc;
+    return launch_lds<mean_small_kernel>(dim3(1), dim3(256), 0, stream, matrix, P, mean_out);
+}
+
+extern "C" int gm3d_patch_chamfer_loss_k_bwd(const void* pred, long long pred_bstride, const float* target, const long long* ids,
+                                             long long ids_bstride, const int32_t* idx1, const int32_t* idx2, const float* gmean, int B,
+                                             int T, int M, int k, int lead, int l1, void* dpred, int dtype, gm3d_stream_t stream) {
+    using namespace gm3d;
+    if (!pred || !target || !ids || !idx1 || !idx2 || !gmean || !dpred || B < 0 || T < 1 || M < 1 || M > T || lead < 0) return GM3D_EINVAL;
+    if (k != 8 && k != 16 && k != 32) return GM3D_EUNSUPPORTED;
+    if (pred_bstride < (long long)M * 3 * k || ids_bstride < M) return GM3D_EINVAL;
+    if (dtype != GM3D_F32 && dtype != GM3D_BF16) return GM3D_EINVAL;
+    if (l1 && lead != 0) return GM3D_EINVAL;
+    if ((long long)B * ((long long)lead + M) * k > 0x7fffffffLL) return GM3D_EUNSUPPORTED;      // B * (lead + M) and B * M * k are formed in int
+    if (B == 0) return GM3D_OK;
+    if (k == 32) {
+        if (l1) return gm3d_patch_chamfer_l1_loss_bwd(pred, pred_bstride, target, ids, ids_bstride, idx1, idx2, gmean, B, T, M, dpred, dtype, stream);
+        return gm3d_patch_chamfer_loss_bwd_full(pred, pred_bstride, target, ids, ids_bstride, idx1, idx2, gmean, B, T, M, lead, dpred, dtype, stream);
+    }
+    const int P = B * (lead + M);
+    return by_int<8, 16>(k, [&](auto c) {
+        constexpr int K = decltype(c)::value, PPB = 256 / K;
+        return by_dtype(dtype, [&](auto* t) {
+            using E = std::remove_pointer_t<decltype(t)>;
+            const dim3 grid((P + PPB - 1) / PPB), block(256);
+            if (l1)
+                return launch_lds<patch_loss_small_bwd_kernel<K, E, true>>(grid, block, 0, stream, (const E*)pred, (size_t)pred_bstride,
+                                                                          target, ids, (size_t)ids_bstride, idx1, idx2, gmean, B, T, M,
+                                                                          (E*)dpred, lead);
+            return launch_lds<patch_loss_small_bwd_kernel<K, E, false>>(grid, block, 0, stream, (const E*)pred, (size_t)pred_bstride,
+                                                                       target, ids, (size_t)ids_bstride, idx1, idx2, gmean, B, T, M,
+                                                                       (E*)dpred, lead);
+        });
     });
 }

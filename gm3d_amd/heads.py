@@ -685,14 +685,14 @@ def rank_loss_tail(pred_full, M, target):
 
 
 class PatchChamferLossFn(torch.autograd.Function):
-    """forward_loss of the north-star model on the masked patches in one pass (csrc/chamfer.hip patch_loss_*): pred (B,M,96) -- a
-    batch-strided view of the decoder head's (B,L,96) output is taken as it is --, target (B,T,32,3) f32, mask_ids (B,M) int64
+    """forward_loss of the north-star model on the masked patches in one pass (csrc/chamfer.hip patch_loss_*): pred (B,M,3k) -- a
+    batch-strided view of the decoder head's (B,L,3k) output is taken as it is --, target (B,T,k,3) f32, k = 8 / 16 / 32, mask_ids (B,M) int64
     -> (Chamfer_mean (), matrix (B,M) f32).  Only Chamfer_mean carries a gradient (the engine detaches `matrix`: it is the teacher's
     ranking target, P/engine_pretrain.py:156-171)."""
 
     @staticmethod
     def forward(ctx, pred, target, mask_ids, full=False):
-        # full=True: pred is the whole (B,L,96) prediction, contiguous; its last M patches enter the loss and the backward returns the
+        # full=True: pred is the whole (B,L,3k) prediction, contiguous; its last M patches enter the loss and the backward returns the
         # gradient of the whole tensor (zeros for the visible patches) -- the [:, -M:] slice and its zero-filling backward folded in
         ctx.set_materialize_grads(False)
         ctx.lead = 0
@@ -700,15 +700,20 @@ class PatchChamferLossFn(torch.autograd.Function):
             ctx.lead = pred.shape[1] - mask_ids.shape[1]
             pred = pred.detach()[:, ctx.lead:]
         B, M, _ = pred.shape
-        T = target.shape[1]
+        T, k = target.shape[1], target.shape[2]
         dev = pred.device
         matrix = torch.empty(B, M, dtype=torch.float32, device=dev)
-        i1 = torch.empty(B * M, 32, dtype=torch.int32, device=dev)
-        i2 = torch.empty(B * M, 32, dtype=torch.int32, device=dev)
+        i1 = torch.empty(B * M, k, dtype=torch.int32, device=dev)
+        i2 = torch.empty(B * M, k, dtype=torch.int32, device=dev)
         mean = torch.empty((), dtype=torch.float32, device=dev)
-        _launch("gm3d_patch_chamfer_loss_fwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_loss_fwd, _ptr(pred),
-                pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), B, T, M, _ptr(matrix), _ptr(i1), _ptr(i2), _ptr(mean),
-                _DT[pred.dtype], _stream())
+        if k == 32:
+            _launch("gm3d_patch_chamfer_loss_fwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_loss_fwd, _ptr(pred),
+                    pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), B, T, M, _ptr(matrix), _ptr(i1), _ptr(i2), _ptr(mean),
+                    _DT[pred.dtype], _stream())
+        else:
+            _launch("gm3d_patch_chamfer_loss_k_fwd", {"B": B, "M": M, "k": k, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_loss_k_fwd,
+                    _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), B, T, M, k, 0, _ptr(matrix), _ptr(i1),
+                    _ptr(i2), _ptr(mean), _DT[pred.dtype], _stream())
         ctx.save_for_backward(pred, target, mask_ids, i1, i2)
         ctx.mark_non_differentiable(matrix)
         return mean, matrix
@@ -717,13 +722,19 @@ class PatchChamferLossFn(torch.autograd.Function):
     def backward(ctx, g, _gm):
         pred, target, mask_ids, i1, i2 = ctx.saved_tensors
         B, M, _ = pred.shape
+        k = target.shape[2]
         if g is None:
             return None, None, None, None
         g = g.detach().reshape(1).float().contiguous()
-        dpred = torch.empty(B, ctx.lead + M, 96, dtype=pred.dtype, device=pred.device)
-        _launch("gm3d_patch_chamfer_loss_bwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_loss_bwd_full, _ptr(pred),
-                pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), _ptr(i1), _ptr(i2), _ptr(g), B, target.shape[1], M,
-                ctx.lead, _ptr(dpred), _DT[pred.dtype], _stream())
+        dpred = torch.empty(B, ctx.lead + M, 3 * k, dtype=pred.dtype, device=pred.device)
+        if k == 32:
+            _launch("gm3d_patch_chamfer_loss_bwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_loss_bwd_full, _ptr(pred),
+                    pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), _ptr(i1), _ptr(i2), _ptr(g), B, target.shape[1], M,
+                    ctx.lead, _ptr(dpred), _DT[pred.dtype], _stream())
+        else:
+            _launch("gm3d_patch_chamfer_loss_k_bwd", {"B": B, "M": M, "k": k, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_loss_k_bwd,
+                    _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), _ptr(i1), _ptr(i2), _ptr(g), B,
+                    target.shape[1], M, k, ctx.lead, 0, _ptr(dpred), _DT[pred.dtype], _stream())
         return dpred, None, None, None
 
 
@@ -735,14 +746,20 @@ class PatchChamferL1LossFn(torch.autograd.Function):
     def forward(ctx, pred, target, mask_ids):
         ctx.set_materialize_grads(False)
         B, M, _ = pred.shape
+        T, k = target.shape[1], target.shape[2]
         dev = pred.device
         matrix = torch.empty(B, M, dtype=torch.float32, device=dev)
-        i1 = torch.empty(B * M, 32, dtype=torch.int32, device=dev)
-        i2 = torch.empty(B * M, 32, dtype=torch.int32, device=dev)
+        i1 = torch.empty(B * M, k, dtype=torch.int32, device=dev)
+        i2 = torch.empty(B * M, k, dtype=torch.int32, device=dev)
         mean = torch.empty((), dtype=torch.float32, device=dev)
-        _launch("gm3d_patch_chamfer_l1_loss_fwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_l1_loss_fwd,
-                _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), B, target.shape[1], M, _ptr(matrix),
-                _ptr(i1), _ptr(i2), _ptr(mean), _DT[pred.dtype], _stream())
+        if k == 32:
+            _launch("gm3d_patch_chamfer_l1_loss_fwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_l1_loss_fwd,
+                    _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), B, T, M, _ptr(matrix),
+                    _ptr(i1), _ptr(i2), _ptr(mean), _DT[pred.dtype], _stream())
+        else:
+            _launch("gm3d_patch_chamfer_l1_loss_k_fwd", {"B": B, "M": M, "k": k, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_loss_k_fwd,
+                    _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), B, T, M, k, 1, _ptr(matrix), _ptr(i1),
+                    _ptr(i2), _ptr(mean), _DT[pred.dtype], _stream())
         ctx.save_for_backward(pred, target, mask_ids, i1, i2)
         ctx.mark_non_differentiable(matrix)
         return mean, matrix
@@ -751,22 +768,32 @@ class PatchChamferL1LossFn(torch.autograd.Function):
     def backward(ctx, g, _gm):
         pred, target, mask_ids, i1, i2 = ctx.saved_tensors
         B, M, _ = pred.shape
+        k = target.shape[2]
         if g is None:
             return None, None, None
         g = g.detach().reshape(1).float().contiguous()
-        dpred = torch.empty(B, M, 96, dtype=pred.dtype, device=pred.device)
-        _launch("gm3d_patch_chamfer_l1_loss_bwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_l1_loss_bwd,
-                _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), _ptr(i1), _ptr(i2), _ptr(g), B,
-                target.shape[1], M, _ptr(dpred), _DT[pred.dtype], _stream())
+        dpred = torch.empty(B, M, 3 * k, dtype=pred.dtype, device=pred.device)
+        if k == 32:
+            _launch("gm3d_patch_chamfer_l1_loss_bwd", {"B": B, "M": M, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_l1_loss_bwd,
+                    _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), _ptr(i1), _ptr(i2), _ptr(g), B,
+                    target.shape[1], M, _ptr(dpred), _DT[pred.dtype], _stream())
+        else:
+            _launch("gm3d_patch_chamfer_l1_loss_k_bwd", {"B": B, "M": M, "k": k, "dtype": str(pred.dtype)}, lib.gm3d_patch_chamfer_loss_k_bwd,
+                    _ptr(pred), pred.stride(0), _ptr(target), _ptr(mask_ids), mask_ids.stride(0), _ptr(i1), _ptr(i2), _ptr(g), B,
+                    target.shape[1], M, k, 0, 1, _ptr(dpred), _DT[pred.dtype], _stream())
         return dpred, None, None
 
 
 FUSED_PATCH_LOSS = True
+PATCH_LOSS_SIZES = (8, 16, 32)      # points per patch the fused loss has kernels for (csrc/chamfer.hip)
 
 
 def patch_chamfer_loss_supported(pred, target, mask_ids):
-    return (FUSED_PATCH_LOSS and pred.is_cuda and pred.dim() == 3 and pred.shape[-1] == 96 and pred.stride(2) == 1 and pred.stride(1) == 96
-            and pred.dtype in _DT and target.dtype == torch.float32 and target.is_contiguous() and tuple(target.shape[2:]) == (32, 3)
+    """pred (B,M,3k), target (B,T,k,3) f32 contiguous, k in 8 / 16 / 32 (PATCH_LOSS_SIZES), mask_ids (B,M) int64"""
+    k = pred.shape[-1] // 3 if pred.dim() == 3 else 0
+    return (FUSED_PATCH_LOSS and pred.is_cuda and k in PATCH_LOSS_SIZES and pred.shape[-1] == 3 * k and pred.stride(2) == 1
+            and pred.stride(1) == 3 * k and pred.dtype in _DT and target.dtype == torch.float32 and target.dim() == 4
+            and target.is_contiguous() and tuple(target.shape[2:]) == (k, 3)
             and mask_ids is not None and mask_ids.dtype == torch.int64 and mask_ids.stride(1) == 1
             and mask_ids.shape == pred.shape[:2] and not target.requires_grad)
 

@@ -136,6 +136,7 @@ FUSED_STACK = True   # False: per-op PyTorch modules below (kept as the in-packa
 FUSED_EMBED = True   # same switch for the mini-PointNet token embed (gm3d_amd/embed.py)
 FUSED_HEADS = True   # ... and for pos_embed, the two heads, the mask-token expand and the ranking loss (gm3d_amd/heads.py)
 MAX_NUM_GROUP = 512  # tokens per cloud the guided-mask and ranking-loss kernels take (csrc/guided.hip); above: the aten formulations
+GROUP_SIZES = (8, 16, 32)  # points per patch the fused masked-patch loss has kernels for (csrc/chamfer.hip, heads.PATCH_LOSS_SIZES)
 
 
 class DropPath(nn.Module):
@@ -361,15 +362,18 @@ class MaskedAutoencoderViT(nn.Module):
     """GM3D Point-MAE (P/:30-188 live part).  The image-MAE constructor arguments are accepted and
     ignored, exactly as the reference ignores them for the point-cloud path (hyper-parameters are the
     literals of P/:110-117), except `num_group` (1..512, the reference's literal 64 by default): the number of FPS centres, i.e. of
-    tokens per cloud."""
+    tokens per cloud, and `group_size` (8, 16 or 32, the reference's literal 32 by default): the points per patch -- the sizes the
+    fused patch loss has kernels for; only the rebuild head's 3 * group_size output rows depend on it."""
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=1024, depth=24, num_heads=16,
                  decoder_embed_dim=512, decoder_depth=8, decoder_num_heads=16, mlp_ratio=4.0,
                  norm_layer=nn.LayerNorm, norm_pix_loss=False, asymmetric_decoder=False, mask_ratio=0.75,
-                 vis_mask_ratio=0.0, saliency=False, num_group=64):
+                 vis_mask_ratio=0.0, saliency=False, num_group=64, group_size=32):
         super().__init__()
         if isinstance(num_group, bool) or int(num_group) != num_group or not 1 <= num_group <= MAX_NUM_GROUP:
             raise ValueError("num_group must be an integer in 1..%d, got %r" % (MAX_NUM_GROUP, num_group))
+        if isinstance(group_size, bool) or int(group_size) != group_size or group_size not in GROUP_SIZES:
+            raise ValueError("group_size must be one of %s, got %r" % (GROUP_SIZES, group_size))
         self.norm_pix_loss = norm_pix_loss
         self.vis_mask_ratio = vis_mask_ratio
         self.encoder_dims = 384
@@ -377,11 +381,10 @@ class MaskedAutoencoderViT(nn.Module):
         self.depth = 12
         self.drop_path_rate = 0.1
         self.num_heads = 6
-        self.group_size = 32
+        self.group_size = int(group_size)    # the reference's literal is 32 (P/:113); 16 and 8 are its config_2 / config_3 patches
         self.decoder_depth = 4
         self.decoder_num_heads = 6
-        self.num_group = int(num_group)      # the reference's literal is 64 (P/:117); group_size stays 32: the fused patch loss and
-                                             # the reconstruction head are built for 32-point patches
+        self.num_group = int(num_group)      # the reference's literal is 64 (P/:117)
 
         self.encoder = Encoder(encoder_channel=self.encoder_dims)
         self.pos_embed = nn.Sequential(nn.Linear(3, 128), nn.GELU(), nn.Linear(128, 384))
@@ -521,7 +524,7 @@ class MaskedAutoencoderViT(nn.Module):
                 from . import heads
                 rebuild_points = heads.LinearBiasFn.apply(x_rec, c.weight, c.bias, heads._adt())
             else:
-                rebuild_points = F.linear(x_rec, c.weight.squeeze(-1), c.bias)  # B L 96
+                rebuild_points = F.linear(x_rec, c.weight.squeeze(-1), c.bias)  # B L 3*group_size
         if side is not None:
             streams.join(side)
             loss_pred_out.record_stream(torch.cuda.current_stream())
@@ -541,8 +544,8 @@ class MaskedAutoencoderViT(nn.Module):
         }
 
     def forward_loss(self, pred, target, mask, mask_ids=None, full_pred=None):
-        """pred (B,M,96) = pix_pred[:, -M:], target = neighborhood (B,G,32,3), mask (B,G) bool (P/:384-412).
-        full_pred: the whole pix_pred (B,L,96) `pred` was sliced from (optional): the fused loss then takes the slice itself and its
+        """pred (B,M,3k) = pix_pred[:, -M:], target = neighborhood (B,G,k,3), k = group_size, mask (B,G) bool (P/:384-412).
+        full_pred: the whole pix_pred (B,L,3k) `pred` was sliced from (optional): the fused loss then takes the slice itself and its
         backward returns the whole tensor's gradient (no separate zero-fill + copy for the slice)."""
         N, t, n, D = target.shape
         M = pred.shape[1]

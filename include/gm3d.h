@@ -146,6 +146,19 @@ int gm3d_patch_chamfer_l1_loss_fwd(const void *pred, long long pred_bstride, con
 int gm3d_patch_chamfer_l1_loss_bwd(const void *pred, long long pred_bstride, const float *target, const long long *ids,
                                    long long ids_bstride, const int32_t *idx1, const int32_t *idx2, const float *gmean, int B, int T,
                                    int M, void *dpred, int dtype, gm3d_stream_t stream);
+/* The same two losses for patches of k points (the reference's config_2 / config_3 geometries: 128 x 16 and 256 x 8): pred
+ * (B, M, 3k), target (B, T, k, 3) f32, idx1 / idx2 (B*M, k) int32, everything else as above.  l1 != 0 selects the `cdl1` value
+ * (sum sqrt d1 + sum sqrt d2) / (2k) and its backward.  k == 32 runs the entry points above (same kernels, same bits); k == 8 / 16
+ * run wave-segment kernels (k lanes per patch, 64 / k patches per wave, no LDS, no atomics, sums in a fixed order); any other k
+ * is GM3D_EUNSUPPORTED.  The backward writes dpred (B, lead + M, 3k) in `dtype`, zeros for the first `lead` patches of every cloud;
+ * lead != 0 with l1 is GM3D_EINVAL (the 32-point `cdl1` backward has no such form).  B == 0 returns GM3D_OK launching nothing;
+ * B * (lead + M) * k <= 2^31 - 1 (GM3D_EUNSUPPORTED beyond).  Every argument is checked on the host before a launch. */
+int gm3d_patch_chamfer_loss_k_fwd(const void *pred, long long pred_bstride, const float *target, const long long *ids,
+                                  long long ids_bstride, int B, int T, int M, int k, int l1, float *matrix, int32_t *idx1,
+                                  int32_t *idx2, float *mean_out, int dtype, gm3d_stream_t stream);
+int gm3d_patch_chamfer_loss_k_bwd(const void *pred, long long pred_bstride, const float *target, const long long *ids,
+                                  long long ids_bstride, const int32_t *idx1, const int32_t *idx2, const float *gmean, int B, int T,
+                                  int M, int k, int lead, int l1, void *dpred, int dtype, gm3d_stream_t stream);
 
 /* Plain LayerNorm over (R, C) rows, 4 <= C <= 512, C % 4 == 0 (nn.LayerNorm of the 96 / 192 / 384-wide Point-M2AE levels):
  * h = (x - mean) * rstd * gamma + beta in `dtype`, mean / rstd (R) f32 saved for the backward.  Backward: dx in `dtype`;
